@@ -12,19 +12,24 @@ CFilter::run, updateThreshold) through pmvs_run_loop, with the model resident in
 value = refined patches/s: patches the expansion refined and committed to the model
 (preProcess -> refinePatch -> postProcess passed, expand.cpp:238) over all ranks / step time.
 Also: NCC evals/s (my_f + computeINCC evaluations), refined candidates/s.
+A plain run sets up, warms up, times --steps steps (ms_per_step = the timed region / steps), writes
+--dump-outputs DIR if given (a fixed sample of the last timed step's model as DIR/<name>.npy; scene,
+seeds and schedule are seeded, so two builds can be compared array for array) and prints the line.
+--full adds the side measurements and checks below (refine_c2, cpu_baseline with the full-size
+parity, checks), each of which takes runs of its own after the timed region.
 roofline: the loop's dominant kernel, refine_split_kernel (the refine batches of >= 10000 candidates):
 algorithmic bytes = 588 B x valid textures per my_f evaluation over its HIP-event
 time, against 8 TB/s HBM; the smaller batches' lane-form kernel (below 7000 candidates) in roofline.small_batches.
-refine_c2: the refine kernel alone on configs[1] (8-view 1920x1080, level 1, 100k candidates).
-cpu_baseline: the same metric on the host CPU -- the oracle (CPU restatement) runs the expansions
+refine_c2 (--full): the refine kernel alone on configs[1] (8-view 1920x1080, level 1, 100k candidates).
+cpu_baseline (--full): the same metric on the host CPU -- the oracle (CPU restatement) runs the expansions
 of the same rank-0 C3 scene from the same models with the same wave schedule (findEmptyBlocks,
 preparation and the refinements of a wave on a std::thread pool over every CPU this process may
 use, commit serial as in the product): the first --cpu-waves waves of iteration 1 and the whole
 expansions of iterations 2 and 3, and a sampled CFilter::run pass per iteration (--cpu-filter-every);
 value = the GPU step's patches over the CPU time the per-iteration rates extrapolate for them.  A refine-only rate over synthetic seed candidates is
 reported beside it (refine_only).
-checks: size-independent properties of the C3 model (identical model from every repetition,
-finite geometry, unit normals, image-list invariants, the synthetic sphere's surface residual).
+checks: the steps' device digests agree (identical model from every repetition); with --full also
+size-independent properties of the fetched C3 model (finite geometry, unit normals, image-list invariants, the synthetic sphere's surface residual).
 
 Multi-GPU (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`), one
 process per GPU:
@@ -123,6 +128,13 @@ def parse():
                     help="loop iterations sampled by the CPU baseline / full-size parity check (1..iterations)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every CPU this process may use")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements and checks: the final model's fetch, "
+                         "sha1 and invariants (checks), the configs[1] refine kernel (refine_c2, unless --no-c2) and "
+                         "the CPU baseline with the full-size oracle parity (cpu_baseline, parity_c3_*, unless "
+                         "--no-cpu-baseline); without it only the headline figure is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the final model, rank 0's) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -349,6 +361,37 @@ def model_checks(model, inp, hashes):
     return checks
 
 
+DUMP_PATCHES = 262144  # --dump-outputs: patches sampled from the model (12 float + 6 int fields each)
+DUMP_LISTS = 8192  # ... the first of them also with their image / vimage lists and grid cells
+
+
+def dump_outputs(out_dir, model):
+    """--dump-outputs: the model the last timed step left (what run_loop returns to its caller) as
+    out_dir/<name>.npy.  A C3 model is 6.7 GB, so a fixed sample is written (52 MB): the
+    patches at DUMP_PATCHES indices drawn without replacement by a seeded generator (in model
+    order; all of them when the model is smaller), every scalar field (floats as float32, integers
+    as float64 -- exact), and for the first DUMP_LISTS of those the image / vimage lists with their
+    grid cells (float32, entries past the patch's count set to -1).  model_size.npy holds the
+    model's patch count, sample_index.npy the sampled indices."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(model)
+    idx = np.arange(n) if n <= DUMP_PATCHES else np.sort(
+        np.random.default_rng(0x0D0B).choice(n, DUMP_PATCHES, replace=False))
+    sample = model[idx]
+    arrays = {"model_size": np.array([n], np.float64), "sample_index": idx.astype(np.float64)}
+    for f in PATCH_SCALARS:
+        x = np.ascontiguousarray(sample[f])
+        arrays[f] = x.astype(np.float32 if x.dtype.kind == "f" else np.float64)
+    head = sample[:DUMP_LISTS]
+    for lst, grd, cnt in (("images", "grids", "num_images"), ("vimages", "vgrids", "num_vimages")):
+        m = np.arange(head[lst].shape[1])[None, :] < head[cnt][:, None]
+        arrays[lst] = np.where(m, head[lst], -1).astype(np.float32)
+        arrays[grd] = np.where(m[:, :, None], head[grd], -1).astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sum(a.nbytes for a in arrays.values())
+
+
 def rank_seed(rank: int) -> int:
     return 0x5EED + 7919 * rank
 
@@ -509,7 +552,7 @@ def main():
     # One step = pmvs_run_loop: seeds up, 3 x (expand, filter), the model left in HBM (as the
     # refine inputs are, the result stays resident); its device digest (pmvs_loop_hash) checks that
     # every repetition gives the same model.  The final model's PCIe fetch (6.7 GB) runs after the
-    # timed region and is reported as fetch_s.
+    # timed region (--full or --dump-outputs only) and is reported as fetch_s.
     def step():
         n_kept, it_log = scene.run_loop(seeds, inp.threshold, iterations=args.iterations, wave=args.wave,
                                         min_candidates=args.min_candidates, fetch=False)
@@ -536,10 +579,16 @@ def main():
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    tf = time.perf_counter()
-    last = scene.loop_fetch(n_last)  # after the timed region
-    fetch_s = time.perf_counter() - tf
-    model_sha1 = hashlib.sha1(last.view(np.uint8)).hexdigest()
+    last = fetch_s = model_sha1 = None
+    if args.full or args.dump_outputs:
+        tf = time.perf_counter()
+        last = scene.loop_fetch(n_last)  # after the timed region
+        fetch_s = time.perf_counter() - tf
+    if args.dump_outputs and rank == 0:
+        nbytes = dump_outputs(args.dump_outputs, last)
+        log(f"outputs of the last timed step written to {args.dump_outputs} ({nbytes / 1e6:.1f} MB)")
+    if args.full:
+        model_sha1 = hashlib.sha1(last.view(np.uint8)).hexdigest()
 
     def tot(key):
         return sum(it["expand"][key] for _, lg in logs for it in lg)
@@ -564,16 +613,20 @@ def main():
 
     result = None
     c2 = None
-    if rank == 0 and not args.no_c2:
+    if rank == 0 and args.full and not args.no_c2:
         c2 = c2_refine(P, args, dev, rank)
     if rank == 0:
-        checks = model_checks(last, inp, hashes)
-        checks["model_digest"] = checks.pop("model_hash")
-        checks["model_hash"] = model_sha1  # sha1 of the fetched final model (the rounds' record format)
+        if args.full:
+            checks = model_checks(last, inp, hashes)
+            checks["model_digest"] = checks.pop("model_hash")
+            checks["model_hash"] = model_sha1  # sha1 of the fetched final model (the rounds' record format)
+        else:  # what the steps' own device digests give; the fetched model's checks need --full
+            same = len(set(hashes)) == 1
+            checks = {"model_identical_across_steps": same, "model_digest": hashes[0] if hashes else None, "ok": same}
         del last
         cpu = parity = None
         first = logs[0][1]
-        if not args.no_cpu_baseline and not shard and not c4:
+        if args.full and not args.no_cpu_baseline and not shard and not c4:
             cpu, parity = loop_samples(P, scene, inp, seeds, args, [it["expand"]["added"] for it in first])
         result = {
             "metric": METRIC,
@@ -582,6 +635,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(elapsed_max / args.steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": "strong" if shard else "weak",
@@ -612,8 +666,9 @@ def main():
             "roofline": roof,
             "stage_s_per_step": {"expand": round(expand_s / args.steps, 3), "filter_device": round(filter_s / args.steps, 3),
                                  "refine_kernel": round(refine_ms / 1e3 / args.steps, 3)},
-            "fetch_s": round(fetch_s, 3),  # the final model's D2H (pmvs_loop_fetch), outside the timed region
-            "value_with_fetch": round(added_all / (elapsed_max + fetch_s * args.steps), 1),
+            # the final model's D2H (pmvs_loop_fetch), outside the timed region; null when it was not fetched
+            "fetch_s": None if fetch_s is None else round(fetch_s, 3),
+            "value_with_fetch": None if fetch_s is None else round(added_all / (elapsed_max + fetch_s * args.steps), 1),
             "iterations": [{"depth": it["depth"], "patches": it["patches"], "added": it["expand"]["added"],
                             "candidates": it["expand"]["candidates"], "waves": it["expand"]["waves"],
                             "expand_ms": round(it["expand"]["wall_ms"], 1),

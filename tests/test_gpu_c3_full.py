@@ -4,7 +4,7 @@ seed candidates with rank_seed(0)):
 
 1. One loop step on the device, its model checked by the bench's size-independent invariants, and
    the first expansion waves of every loop iteration compared record for record with the CPU
-   oracle (bench.py loop_samples -> parity_c3_first_waves; bench.py exits 3 on a mismatch).
+   oracle (bench.py --full: loop_samples -> parity_c3_first_waves; it exits 3 on a mismatch).
 2. One whole CFilter::run pass at 4K (filter.cpp:13-27: filterOutside, filterExact, filterNeighbor,
    filterSmallGroups over 104 M cells): the device's iteration-1 model (the full first expansion,
    about 4.2 M patches) filtered on the device and by the oracle's filter_run -- keep flags, counts
@@ -45,7 +45,7 @@ def test_c3_full_size_step_and_first_waves_match_oracle(c3):
     assert checks["ok"] and checks["sphere_residual_p99"] < 0.01, checks
     assert log[0]["expand"]["added"] > 3_000_000
     del model
-    # iteration 1 here (every bench.py run samples all three iterations: parity_c3_first_waves)
+    # iteration 1 here (every bench.py --full run samples all three iterations: parity_c3_first_waves)
     args = argparse.Namespace(iterations=3, cpu_iterations=1, cpu_waves=2, cpu_waves_late=0, cpu_seconds=1.0,
                               cpu_threads=0, cpu_filter_every=0, wave=32768, min_candidates=131072)
     _, parity = bench.loop_samples(P, scene, inp, seeds, args, [it["expand"]["added"] for it in log])

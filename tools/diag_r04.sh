@@ -7,7 +7,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/${1:-r04c}; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-PMVS_EXPAND_PROFILE=1 timeout -k 10 300 python3 -u $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-c2 > $O/phase.json 2> $O/phase.err && \
+PMVS_EXPAND_PROFILE=1 timeout -k 10 300 python3 -u $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-c2 > $O/phase.json 2> $O/phase.err && \
 PMVS_AMD_LIB=$R/cmvs-pmvs_amd/libpmvs_amd_prof.so PMVS_REFINE_CONFIG=1206 timeout -k 10 200 python3 -u $R/tools/refine_phases.py 1000 5000 20000 100000 > $O/phases_1206.jsonl 2> $O/phases.err && \
 timeout -k 10 300 python3 -u $R/tools/refine_sizes.py 1206,132042 2000,5000,10000,20000,40000,80000,120000 > $O/sizes_main.jsonl 2> $O/sizes.err && \
 PMVS_AMD_LIB=$R/cmvs-pmvs_amd/libpmvs_amd_bqp.so timeout -k 10 300 python3 -u $R/tools/refine_sizes.py 2448,2432,1232 10000,20000,40000,80000,120000 > $O/sizes_bqp.jsonl 2>> $O/sizes.err && \

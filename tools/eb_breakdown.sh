@@ -11,6 +11,6 @@ for v in main ebsort ebbin ebwalk; do
   L=$R/cmvs-pmvs_amd/libpmvs_amd_$v.so
   [ "$v" = main ] && L=$R/cmvs-pmvs_amd/libpmvs_amd.so
   PMVS_AMD_LIB=$L timeout -k 10 240 rocprofv3 --kernel-trace --output-format csv -d $O/$v -o run -- \
-    python3 $R/bench.py --steps 1 --warmup 0 --iterations 1 --no-c2 --no-cpu-baseline > $O/$v.json 2> $O/$v.err || exit 1
+    python3 $R/bench.py --full --steps 1 --warmup 0 --iterations 1 --no-c2 --no-cpu-baseline > $O/$v.json 2> $O/$v.err || exit 1
 done
 echo breakdown done

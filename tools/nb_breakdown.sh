@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in main nbsort nblls nbboth; do
   L=$R/cmvs-pmvs_amd/libpmvs_amd_$v.so
   [ "$v" = main ] && L=$R/cmvs-pmvs_amd/libpmvs_amd.so
-  PMVS_AMD_LIB=$L timeout -k 10 240 python3 $R/bench.py --steps 1 --warmup 0 --iterations 1 --no-c2 --no-cpu-baseline \
+  PMVS_AMD_LIB=$L timeout -k 10 240 python3 $R/bench.py --full --steps 1 --warmup 0 --iterations 1 --no-c2 --no-cpu-baseline \
     > $O/$v.json 2> $O/$v.err || exit 1
   echo "$v $(python3 -c "import json; d=json.load(open('$O/$v.json')); print(d['iterations'][0]['filter_ms'], d['ms_per_step'])")"
 done

@@ -2,7 +2,7 @@ set -o pipefail
 O=$(pwd)/gpurun_out/r05n; mkdir -p $O
 R=$(pwd)
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --hip-trace --kernel-trace --stats --output-format csv -d $O/ht -o run -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-c2 > $O/ht.log 2>&1
+timeout -k 10 400 rocprofv3 --hip-trace --kernel-trace --stats --output-format csv -d $O/ht -o run -- python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-c2 > $O/ht.log 2>&1
 rc=$?
 cd $O/ht && python3 - <<'PY' > $O/api_summary.txt
 import csv, glob, re

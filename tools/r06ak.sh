@@ -8,5 +8,5 @@ tail -3 $O/gpu_tests.txt
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 120 python3 -u -c "import __graft_entry__ as g; g.smoke()" >> $O/gpu_tests.txt 2>&1 || { echo SMOKE_FAIL; exit 1; }
 tail -1 $O/gpu_tests.txt
-timeout -k 10 250 python3 -u bench.py > $O/bench.json 2> $O/bench.err || { echo BENCH_FAIL; tail -5 $O/bench.err; exit 1; }
+timeout -k 10 250 python3 -u bench.py --full > $O/bench.json 2> $O/bench.err || { echo BENCH_FAIL; tail -5 $O/bench.err; exit 1; }
 tail -1 $O/bench.json | cut -c1-400

@@ -2,7 +2,7 @@
 # C3 loop A/B: the small refine batches on the workgroup form (default) or the lane form, split point
 set -o pipefail
 O=gpurun_out/r06d; mkdir -p $O
-B="python3 -u bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-c2"
+B="python3 -u bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-c2"
 ( while true; do sleep 50; echo "alive $(date +%T)" >> $O/heartbeat.txt; done ) & HB=$!
 trap 'kill $HB 2>/dev/null' EXIT
 for v in base:132042:10000 lane10k:300000:10000 lane7k:300000:7000 lane5k:300000:5000; do

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 ( while true; do sleep 50; echo "alive $(date +%T)" >> $O/heartbeat.txt; done ) & HB=$!
 trap 'kill $HB 2>/dev/null' EXIT
 for G in ${GS:-2 1 0}; do
-  PMVS_COMMIT_GRID_ROUNDS=$G timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt$G -o run -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-c2 > $O/b$G.out 2> $O/b$G.err || { echo "B${G}_FAIL"; tail $O/b$G.err; exit 1; }
+  PMVS_COMMIT_GRID_ROUNDS=$G timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt$G -o run -- python3 $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-c2 > $O/b$G.out 2> $O/b$G.err || { echo "B${G}_FAIL"; tail $O/b$G.err; exit 1; }
   python3 $R/tools/ktsum.py $O/kt$G > $O/kt${G}_summary.json && rm -rf $O/kt$G || exit 1
   python3 - $O $G <<'PY' || exit 1
 import json, sys

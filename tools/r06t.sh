@@ -10,5 +10,5 @@ cd $R && timeout -k 10 320 python3 -u -m pytest "tests/test_gpu_c5_exchange.py::
 grep -E "C5 cluster|passed|failed|s call" $O/pytest.log | cut -c1-400
 timeout -k 10 120 python3 -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo SMOKE_FAIL; tail $O/smoke.log; exit 1; }
 tail -2 $O/smoke.log
-timeout -k 10 500 python3 -u bench.py > $O/bench.log 2> $O/bench.err || { echo BENCH_FAIL; tail -20 $O/bench.err; exit 1; }
+timeout -k 10 500 python3 -u bench.py --full > $O/bench.log 2> $O/bench.err || { echo BENCH_FAIL; tail -20 $O/bench.err; exit 1; }
 tail -1 $O/bench.log | cut -c1-1500

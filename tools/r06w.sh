@@ -4,7 +4,7 @@
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/r06w; mkdir -p $O
-cd $R && PMVS_AMD_LIB=$R/cmvs-pmvs_amd/libpmvs_amd_nbprof.so timeout -k 10 300 python3 -u bench.py --steps 1 --warmup 0 --no-c2 --no-cpu-baseline \
+cd $R && PMVS_AMD_LIB=$R/cmvs-pmvs_amd/libpmvs_amd_nbprof.so timeout -k 10 300 python3 -u bench.py --full --steps 1 --warmup 0 --no-c2 --no-cpu-baseline \
   > $O/bench.json 2> $O/bench.err || { echo BENCH_FAIL; tail -20 $O/bench.err; exit 1; }
 grep nb_prof $O/bench.err
 python3 -c "import json; d=json.load(open('$O/bench.json')); print(d['ms_per_step'], [round(i['filter_ms']) for i in d['iterations']], d['checks']['model_hash'][:12])"

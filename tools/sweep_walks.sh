@@ -10,7 +10,7 @@ for lib in ${2:-main}; do
   i=$((i+1))
   L=$R/cmvs-pmvs_amd/libpmvs_amd_$lib.so
   [ "$lib" = main ] && L=$R/cmvs-pmvs_amd/libpmvs_amd.so
-  PMVS_AMD_LIB=$L timeout -k 10 240 python3 $R/bench.py --steps ${STEPS:-1} --warmup ${WARMUP:-0} --no-c2 --no-cpu-baseline \
+  PMVS_AMD_LIB=$L timeout -k 10 240 python3 $R/bench.py --full --steps ${STEPS:-1} --warmup ${WARMUP:-0} --no-c2 --no-cpu-baseline \
     > $O/$lib.$i.json 2> $O/$lib.$i.err || exit 1
   echo "$lib $(python3 -c "import json; d=json.load(open('$O/$lib.$i.json')); it=d['iterations']; print(d['ms_per_step'], [round(i['filter_ms']) for i in it], [round(i.get('expand_ms',0)) for i in it], d['checks']['model_hash'][:12])")"
 done
