@@ -7,7 +7,8 @@
 //
 // Pipeline: option file -> images (PPM / JPEG), masks, edges, cameras -> pmvs_scene_create (device
 // pyramids) -> pmvs_detect_features (Harris + DoG on the device) -> pmvs_seed_run (seed phase) ->
-// pmvs_run_loop (3 x expand / filter, model resident in HBM) -> writers (colours on the device).
+// pmvs_run_loop (3 x expand / filter, model resident in HBM) -> pmvs_loop_export (writer order, fields,
+// lists and colours on the device) -> writers.
 //
 // Multi-rank jobs (CMVS cluster per GPU): with WORLD_SIZE > 1 in the environment
 // (torchrun-style: RANK, WORLD_SIZE, LOCAL_RANK, MASTER_ADDR, MASTER_PORT; genOption --gpus N writes
@@ -294,12 +295,6 @@ int main(int argc, char* argv[]) {
       CHECK("cluster", pmvs_scene_set_cluster(sc, job.rank, job.world, images.data(), &pmvs_tcp_allgather, job.tcp));
     }
   }
-  std::vector<int> gwidth(num);  // _gwidths (patchOrganizerS.cpp:54-87)
-  for (int i = 0; i < num; ++i) {
-    int w = views[i].w;
-    for (int l = 0; l < opt->level; ++l) w /= 2;
-    gwidth[i] = (w + opt->csize - 1) / opt->csize;
-  }
   std::vector<View>().swap(views);  // level-0 images live on the device now
   const double t_init = now_s();
 
@@ -348,9 +343,6 @@ int main(int argc, char* argv[]) {
   int32_t nmodel = 0;
   CHECK("expand/filter", pmvs_run_loop(sc, seeds.data(), nseeds, opt->threshold, iterations, wave, min_cands,
                                        PMVS_EXPAND_AFTER_SEEDS, INT_MAX / 2, &nmodel, it.data()));
-  std::vector<pmvs_patch> model(std::max(nmodel, 1));
-  CHECK("fetch", pmvs_loop_fetch(sc, model.data(), nmodel));
-  model.resize(nmodel);
   for (int t = 0; t < iterations; ++t)
     std::cerr << "depth " << it[t].depth << ": expanded " << it[t].expand.added << ", kept " << it[t].patches
               << (job.world > 1 ? ", boundary sent " + std::to_string(it[t].boundary_sent) + " received " +
@@ -363,40 +355,35 @@ int main(int argc, char* argv[]) {
   // ---- CPatchOrganizerS::writePatches2 (patchOrganizerS.cpp:89-132): collectPatches(1)
   // (patchOrganizerS.cpp:207-236) walks target images, their cells in raster order and each cell's
   // list in insertion (= model) order, taking every patch at its first registration: the key is
-  // (lowest target image holding the patch, its cell there), ties in model order.
-  std::vector<long long> key(nmodel);
-  for (int p = 0; p < nmodel; ++p) {
-    const pmvs_patch& q = model[p];
-    int bt = INT_MAX, k0 = -1;
-    for (int k = 0; k < q.num_images; ++k)
-      if (q.images[k] < tnum && q.images[k] < bt) { bt = q.images[k]; k0 = k; }
-    key[p] = k0 < 0 ? LLONG_MAX
-                    : ((long long)bt << 40) + (long long)q.grids[k0][1] * gwidth[bt] + q.grids[k0][0];
+  // (lowest target image holding the patch, its cell there), ties in model order.  The order, the
+  // writers' fields and lists (index2image applied) and writePLY's colours are produced on the
+  // device (pmvs_loop_export): only these arrays cross PCIe, not the model's records.
+  pmvs_export_sizes xs{};
+  CHECK("export", pmvs_loop_export_sizes(sc, &xs));
+  std::vector<float> fields((size_t)std::max(nmodel, 1) * 11);
+  std::vector<int32_t> colors((size_t)std::max(nmodel, 1) * 3);
+  std::vector<int64_t> ioff, voff;  // the lists only for the .patch file
+  std::vector<int32_t> ids, vids;
+  pmvs_export_buffers xb{};
+  xb.fields = fields.data();
+  xb.colors = colors.data();
+  if (export_patch) {
+    ioff.resize((size_t)nmodel + 1);
+    voff.resize((size_t)nmodel + 1);
+    ids.resize((size_t)std::max<int64_t>(xs.image_entries, 1));
+    vids.resize((size_t)std::max<int64_t>(xs.vimage_entries, 1));
+    xb.image_off = ioff.data();
+    xb.image_ids = ids.data();
+    xb.vimage_off = voff.data();
+    xb.vimage_ids = vids.data();
   }
-  std::vector<int> order(nmodel);
-  for (int p = 0; p < nmodel; ++p) order[p] = p;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key[a] < key[b]; });
-  std::vector<float> fields((size_t)nmodel * 11);
-  std::vector<int32_t> nimg(nmodel), nvimg(nmodel), ids, vids, idx;
-  for (int r = 0; r < nmodel; ++r) {
-    const pmvs_patch& q = model[order[r]];
-    float* f = fields.data() + (size_t)r * 11;
-    for (int k = 0; k < 4; ++k) { f[k] = q.coord[k]; f[4 + k] = q.normal[k]; }
-    f[8] = q.ncc; f[9] = q.dscale; f[10] = q.ascale;
-    nimg[r] = q.num_images;
-    nvimg[r] = q.num_vimages;
-    for (int k = 0; k < q.num_images; ++k) {
-      ids.push_back(images[q.images[k]]);  // index2image
-      idx.push_back(q.images[k]);
-    }
-    for (int k = 0; k < q.num_vimages; ++k) vids.push_back(images[q.vimages[k]]);
+  CHECK("export", pmvs_loop_export(sc, PMVS_EXPORT_WRITER_ORDER, images.data(), &xb));
+  std::vector<int32_t> nimg(nmodel), nvimg(nmodel);
+  for (int r = 0; r < nmodel && export_patch; ++r) {
+    nimg[r] = (int32_t)(ioff[r + 1] - ioff[r]);
+    nvimg[r] = (int32_t)(voff[r + 1] - voff[r]);
   }
   const std::string out = prefix + "models/" + option;
-  std::vector<float> coords((size_t)std::max(nmodel, 1) * 4);
-  for (int r = 0; r < nmodel; ++r)
-    for (int k = 0; k < 4; ++k) coords[(size_t)4 * r + k] = fields[(size_t)r * 11 + k];
-  std::vector<int32_t> colors((size_t)std::max(nmodel, 1) * 3);
-  if (nmodel) CHECK("colours", pmvs_patch_colors(sc, nmodel, coords.data(), nimg.data(), idx.data(), colors.data()));
   CHECK("ply", pmvs_write_ply((out + ".ply").c_str(), nmodel, fields.data(), colors.data()));
   if (export_patch)
     CHECK("patch", pmvs_write_patches((out + ".patch").c_str(), nmodel, fields.data(), nimg.data(), ids.data(),

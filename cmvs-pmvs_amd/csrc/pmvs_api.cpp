@@ -1438,6 +1438,157 @@ pmvs_status pmvs_loop_hash(pmvs_scene* sc, uint64_t* hash) {
   return PMVS_OK;
 }
 
+// ---- model export (pmvs_export.hip)
+namespace {
+struct ExportTemp {  // device memory of one export call, freed when the call returns
+  std::vector<void*> ptrs;
+  template <class T>
+  hipError_t alloc(T** p, size_t count) {
+    void* v = nullptr;
+    const hipError_t e = hipMalloc(&v, std::max(count, (size_t)1) * sizeof(T));
+    if (e == hipSuccess) ptrs.push_back(v);
+    *p = static_cast<T*>(v);
+    return e;
+  }
+  ~ExportTemp() {
+    for (void* p : ptrs) (void)hipFree(p);
+  }
+};
+
+pmvs_status export_status(hipError_t e, const char* what) {
+  if (e == hipErrorOutOfMemory) return fail(PMVS_ENOMEM, "%s: %s", what, hipGetErrorString(e));
+  return fail(PMVS_EDEVICE, "%s: %s", what, hipGetErrorString(e));
+}
+#define EXPCHK(expr)                                         \
+  do {                                                       \
+    const hipError_t e_ = (expr);                            \
+    if (e_ != hipSuccess) return export_status(e_, #expr);   \
+  } while (0)
+
+pmvs_status check_export_patches(const pmvs_scene* sc, const pmvs_patch* patches, int32_t n, pmvs_export_sizes* sizes) {
+  long long ni = 0, nv = 0;
+  for (int i = 0; i < n; ++i) {
+    const pmvs_patch& p = patches[i];
+    if (p.num_images < 1 || p.num_images > PMVS_MAX_IMAGES || p.num_vimages < 0 || p.num_vimages > PMVS_MAX_IMAGES)
+      return fail(PMVS_EINVAL, "patch %d: image counts", i);
+    for (int k = 0; k < p.num_images; ++k)
+      if (p.images[k] < 0 || p.images[k] >= sc->ds.num) return fail(PMVS_EINVAL, "patch %d: image %d", i, p.images[k]);
+    for (int k = 0; k < p.num_vimages; ++k)
+      if (p.vimages[k] < 0 || p.vimages[k] >= sc->ds.tnum) return fail(PMVS_EINVAL, "patch %d: vimage", i);
+    ni += p.num_images;
+    nv += p.num_vimages;
+  }
+  if (sizes) *sizes = pmvs_export_sizes{n, 0, ni, nv};
+  return PMVS_OK;
+}
+
+pmvs_status device_export_sizes(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, pmvs_export_sizes* sizes) {
+  ExportTemp tmp;
+  unsigned long long* d_tot = nullptr;
+  unsigned long long tot[2] = {0, 0};
+  EXPCHK(tmp.alloc(&d_tot, 2));
+  EXPCHK(export_sizes(dP, n, d_tot, sc->stream));
+  EXPCHK(hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, sc->stream));
+  EXPCHK(hipStreamSynchronize(sc->stream));
+  *sizes = pmvs_export_sizes{n, 0, (int64_t)tot[0], (int64_t)tot[1]};
+  return PMVS_OK;
+}
+
+// The export of the device records dP[0, n); sz = their totals.
+pmvs_status export_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, const pmvs_export_sizes& sz, int32_t flags,
+                           const int32_t* index2image, const pmvs_export_buffers* b) {
+  const bool dev = (flags & PMVS_EXPORT_DEVICE) != 0;
+  if (n == 0) {  // offsets {0}
+    int64_t* const offs[2] = {b->image_off, b->vimage_off};
+    for (int64_t* off : offs) {
+      if (off && dev) EXPCHK(hipMemsetAsync(off, 0, sizeof(int64_t), sc->stream));
+      if (off && !dev) *off = 0;
+    }
+    if (dev) EXPCHK(hipStreamSynchronize(sc->stream));
+    return PMVS_OK;
+  }
+  ExportTemp tmp;
+  int* d_tab = nullptr;
+  if (index2image) {
+    EXPCHK(tmp.alloc(&d_tab, (size_t)sc->ds.num));
+    EXPCHK(hipMemcpyAsync(d_tab, index2image, (size_t)sc->ds.num * sizeof(int), hipMemcpyHostToDevice, sc->stream));
+  }
+  int max_gwidth = 1;
+  for (int t = 0; t < sc->ds.tnum; ++t)
+    max_gwidth = std::max(max_gwidth, (sc->hviews[t].w[sc->ds.level] + sc->ds.csize - 1) / sc->ds.csize);
+  static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "export array types");
+  const size_t np = (size_t)n, ne = (size_t)sz.image_entries, nve = (size_t)sz.vimage_entries;
+  ExportArrays a;
+  if (dev) {  // straight into the caller's device buffers
+    a.fields = b->fields; a.colors = b->colors; a.image_off = (long long*)b->image_off; a.image_ids = b->image_ids;
+    a.image_idx = b->image_idx; a.vimage_off = (long long*)b->vimage_off; a.vimage_ids = b->vimage_ids; a.source = b->source;
+  } else {    // device staging for the requested arrays
+    if (b->fields) EXPCHK(tmp.alloc(&a.fields, np * 11));
+    if (b->colors) EXPCHK(tmp.alloc(&a.colors, np * 3));
+    if (b->image_off) EXPCHK(tmp.alloc(&a.image_off, np + 1));
+    if (b->image_ids) EXPCHK(tmp.alloc(&a.image_ids, ne));
+    if (b->image_idx) EXPCHK(tmp.alloc(&a.image_idx, ne));
+    if (b->vimage_off) EXPCHK(tmp.alloc(&a.vimage_off, np + 1));
+    if (b->vimage_ids) EXPCHK(tmp.alloc(&a.vimage_ids, nve));
+    if (b->source) EXPCHK(tmp.alloc(&a.source, np));
+  }
+  EXPCHK(export_pass(sc->ds, dP, n, (flags & PMVS_EXPORT_WRITER_ORDER) != 0, max_gwidth, d_tab, a, sc->stream));
+  if (!dev) {
+    auto down = [&](void* dst, const void* src, size_t bytes) {
+      return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sc->stream) : hipSuccess;
+    };
+    EXPCHK(down(b->fields, a.fields, np * 11 * sizeof(float)));
+    EXPCHK(down(b->colors, a.colors, np * 3 * sizeof(int32_t)));
+    EXPCHK(down(b->image_off, a.image_off, (np + 1) * sizeof(int64_t)));
+    EXPCHK(down(b->image_ids, a.image_ids, ne * sizeof(int32_t)));
+    EXPCHK(down(b->image_idx, a.image_idx, ne * sizeof(int32_t)));
+    EXPCHK(down(b->vimage_off, a.vimage_off, (np + 1) * sizeof(int64_t)));
+    EXPCHK(down(b->vimage_ids, a.vimage_ids, nve * sizeof(int32_t)));
+    EXPCHK(down(b->source, a.source, np * sizeof(int32_t)));
+    EXPCHK(hipStreamSynchronize(sc->stream));
+  }
+  return PMVS_OK;
+}
+}  // namespace
+
+pmvs_status pmvs_loop_export_sizes(pmvs_scene* sc, pmvs_export_sizes* sizes) {
+  if (!sc || !sizes) return fail(PMVS_EINVAL, "invalid argument");
+  if (sc->lkept < 0) return fail(PMVS_EINVAL, "loop_export_sizes: no loop result on the device");
+  HIPCHK(hipSetDevice(sc->device));
+  return device_export_sizes(sc, sc->fpatches.p, sc->lkept, sizes);
+}
+
+pmvs_status pmvs_loop_export(pmvs_scene* sc, int32_t flags, const int32_t* index2image, const pmvs_export_buffers* buffers) {
+  if (!sc || !buffers || (flags & ~(PMVS_EXPORT_WRITER_ORDER | PMVS_EXPORT_DEVICE))) return fail(PMVS_EINVAL, "invalid argument");
+  if (sc->lkept < 0) return fail(PMVS_EINVAL, "loop_export: no loop result on the device");
+  HIPCHK(hipSetDevice(sc->device));
+  pmvs_export_sizes sz{};
+  if (pmvs_status st = device_export_sizes(sc, sc->fpatches.p, sc->lkept, &sz)) return st;
+  return export_records(sc, sc->fpatches.p, sc->lkept, sz, flags, index2image, buffers);
+}
+
+pmvs_status pmvs_export_patches_sizes(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, pmvs_export_sizes* sizes) {
+  if (!sc || !sizes || n < 0 || (n > 0 && !patches)) return fail(PMVS_EINVAL, "invalid argument");
+  return check_export_patches(sc, patches, n, sizes);
+}
+
+pmvs_status pmvs_export_patches(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, int32_t flags,
+                                const int32_t* index2image, const pmvs_export_buffers* buffers) {
+  if (!sc || !buffers || n < 0 || (n > 0 && !patches) || (flags & ~(PMVS_EXPORT_WRITER_ORDER | PMVS_EXPORT_DEVICE)))
+    return fail(PMVS_EINVAL, "invalid argument");
+  pmvs_export_sizes sz{};
+  if (pmvs_status st = check_export_patches(sc, patches, n, &sz)) return st;
+  HIPCHK(hipSetDevice(sc->device));
+  // a buffer of its own: sc->fpatches may hold a loop result
+  ExportTemp tmp;
+  pmvs_patch* dP = nullptr;
+  if (n) {
+    EXPCHK(tmp.alloc(&dP, (size_t)n));
+    EXPCHK(hipMemcpyAsync(dP, patches, (size_t)n * sizeof(pmvs_patch), hipMemcpyHostToDevice, sc->stream));
+  }
+  return export_records(sc, dP, n, sz, flags, index2image, buffers);
+}
+
 pmvs_status pmvs_scene_set_shard(pmvs_scene* sc, int32_t rank, int32_t world, pmvs_allgather_fn fn, void* ctx) {
   if (!sc || world < 1 || rank < 0 || rank >= world || (world > 1 && !fn)) return fail(PMVS_EINVAL, "invalid shard");
   sc->shard_rank = rank;

@@ -65,6 +65,25 @@ hipError_t launch_model_digest(const void* recs, int n, int record_bytes, unsign
 hipError_t launch_patch_colors(const DScene& s, int n, const float* coords, const int* off, const int* images, int* out,
                                hipStream_t stream);
 
+// ---- model export (pmvs_export.hip)
+// Device pointers of the arrays of pmvs_export_buffers (include/pmvs_amd.h); null = not wanted.
+struct ExportArrays {
+  float* fields = nullptr;
+  int* colors = nullptr;
+  long long* image_off = nullptr;
+  int *image_ids = nullptr, *image_idx = nullptr;
+  long long* vimage_off = nullptr;
+  int *vimage_ids = nullptr, *source = nullptr;
+};
+// d_tot[0] / d_tot[1] = the records' num_images / num_vimages summed (queued on st).
+hipError_t export_sizes(const pmvs_patch* P, int n, unsigned long long* d_tot, hipStream_t st);
+// The records P[0, n) as the arrays of `out`, rows in collectPatches(1) order (writer_order) or model
+// order; max_gwidth = the widest target cell grid (sizes the sort key), d_tab = index2image on the
+// device or null (identity).  Returns after the stream has finished the work; hipErrorOutOfMemory when
+// its scratch cannot be allocated.
+hipError_t export_pass(const DScene& s, const pmvs_patch* P, int n, bool writer_order, int max_gwidth, const int* d_tab,
+                       const ExportArrays& out, hipStream_t st);
+
 // ---- filter pass (pmvs_filter.hip)
 // Page-locked host staging (hipHostMalloc), grown on demand: the large per-pass downloads
 // (filterSmallGroups' edge lists, the expansion queue's initial order) at full PCIe rate.

@@ -102,6 +102,19 @@ class LoopIter(C.Structure):
                                                       "inserted": self.boundary_inserted}}
 
 
+class ExportSizes(C.Structure):  # pmvs_export_sizes
+    _fields_ = [("patches", C.c_int32), ("reserved", C.c_int32), ("image_entries", C.c_int64),
+                ("vimage_entries", C.c_int64)]
+
+
+class ExportBuffers(C.Structure):  # pmvs_export_buffers
+    _fields_ = [(k, C.c_void_p) for k in ("fields", "colors", "image_off", "image_ids", "image_idx", "vimage_off",
+                                          "vimage_ids", "source")]
+
+
+EXPORT_WRITER_ORDER, EXPORT_DEVICE = 1, 2
+
+
 class SeedStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("trial", "pass_", "fail0", "fail1", "refined", "rounds", "candidates",
                                           "reserved")] + [(k, C.c_double) for k in ("wall_ms", "gen_ms", "refine_ms")]
@@ -143,7 +156,9 @@ EXPORTS = ["pmvs_last_error", "pmvs_device_count", "pmvs_scene_create", "pmvs_sc
            "pmvs_synth_candidates", "pmvs_selftest_math", "pmvs_selftest_bobyqa", "pmvs_camera_load",
            "pmvs_ppm_load", "pmvs_options_load", "pmvs_options_free", "pmvs_write_patches", "pmvs_write_pset",
            "pmvs_write_ply", "pmvs_patch_colors", "pmvs_filter_run",
-           "pmvs_expand_run", "pmvs_expand_fetch", "pmvs_run_loop", "pmvs_loop_fetch", "pmvs_loop_hash", "pmvs_scene_set_shard", "pmvs_scene_set_shard_rccl", "pmvs_scene_set_cluster",
+           "pmvs_expand_run", "pmvs_expand_fetch", "pmvs_run_loop", "pmvs_loop_fetch", "pmvs_loop_hash",
+           "pmvs_loop_export_sizes", "pmvs_loop_export", "pmvs_export_patches_sizes", "pmvs_export_patches",
+           "pmvs_scene_set_shard", "pmvs_scene_set_shard_rccl", "pmvs_scene_set_cluster",
            "pmvs_scene_set_cluster_rccl", "pmvs_rccl_unique_id",
            "pmvs_rccl_create", "pmvs_rccl_destroy", "pmvs_rccl_allgather", "pmvs_rccl_allgather_device",
            "pmvs_tcp_create", "pmvs_tcp_allgather", "pmvs_tcp_destroy", "pmvs_thread_exchange_create",
@@ -209,6 +224,11 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                                   C.c_int32, C.POINTER(C.c_int32), C.c_void_p]
     lib.pmvs_loop_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     lib.pmvs_loop_hash.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.pmvs_loop_export_sizes.argtypes = [C.c_void_p, C.POINTER(ExportSizes)]
+    lib.pmvs_loop_export.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(ExportBuffers)]
+    lib.pmvs_export_patches_sizes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(ExportSizes)]
+    lib.pmvs_export_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                        C.POINTER(ExportBuffers)]
     lib.pmvs_scene_set_shard.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.pmvs_scene_set_cluster.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pmvs_scene_set_cluster_rccl.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
@@ -353,6 +373,7 @@ class Scene:
         h = C.c_void_p()
         _check(self.lib.pmvs_scene_create(C.byref(self.desc), device, C.byref(h)))
         self.handle = h
+        self.device = device
         self.wsize = inputs.wsize
 
     def close(self):
@@ -528,6 +549,67 @@ class Scene:
         h = C.c_uint64(0)
         _check(self.lib.pmvs_loop_hash(self.handle, C.byref(h)))
         return int(h.value)
+
+    # pmvs_export_buffers: array name -> (dtype, shape from (patches, image entries, vimage entries))
+    EXPORT_ARRAYS = {"fields": ("float32", lambda n, e, v: (n, 11)), "colors": ("int32", lambda n, e, v: (n, 3)),
+                     "image_off": ("int64", lambda n, e, v: (n + 1,)), "image_ids": ("int32", lambda n, e, v: (e,)),
+                     "image_idx": ("int32", lambda n, e, v: (e,)), "vimage_off": ("int64", lambda n, e, v: (n + 1,)),
+                     "vimage_ids": ("int32", lambda n, e, v: (v,)), "source": ("int32", lambda n, e, v: (n,))}
+
+    def _export_buffers(self, sizes: ExportSizes, device: bool, arrays):
+        """The arrays of one export (numpy, or torch tensors on the scene's device) and the
+        pmvs_export_buffers that points at them; names not in `arrays` stay NULL."""
+        names = list(self.EXPORT_ARRAYS) if arrays is None else list(arrays)
+        out, buf = {}, ExportBuffers()
+        for k in names:
+            dt, shape = self.EXPORT_ARRAYS[k]
+            shape = shape(sizes.patches, sizes.image_entries, sizes.vimage_entries)
+            if device:
+                import torch
+                out[k] = torch.empty(shape, dtype=getattr(torch, dt), device=torch.device("cuda", self.device))
+                setattr(buf, k, out[k].data_ptr() if out[k].numel() else None)
+            else:
+                out[k] = np.empty(shape, dt)
+                setattr(buf, k, out[k].ctypes.data if out[k].size else None)
+        return out, buf
+
+    @staticmethod
+    def _index2image(index2image):
+        return None if index2image is None else np.ascontiguousarray(index2image, np.int32)
+
+    def loop_export_sizes(self) -> dict:
+        """pmvs_loop_export_sizes: patches and list entries of the loop result on the device."""
+        sz = ExportSizes()
+        _check(self.lib.pmvs_loop_export_sizes(self.handle, C.byref(sz)))
+        return {"patches": sz.patches, "image_entries": sz.image_entries, "vimage_entries": sz.vimage_entries}
+
+    def loop_export(self, writer_order: bool = True, index2image=None, device: bool = False, arrays=None) -> dict:
+        """pmvs_loop_export: the last run_loop(fetch=False) result as compact arrays, keyed by the
+        fields of pmvs_export_buffers (fields [n, 11], colors [n, 3], image_off [n + 1], image_ids,
+        image_idx, vimage_off [n + 1], vimage_ids, source [n]); rows in the order pmvs2 writes
+        (writer_order) or in model order.  Does not consume the result.  index2image: the image number
+        of every view (None = the view indexes).  device=True: torch tensors allocated on the scene's
+        device and written there (no host copy; import torch before the first Scene when torch ships
+        its own HIP runtime, as bench.py does).  arrays: the names wanted (None = all)."""
+        sz = ExportSizes()
+        _check(self.lib.pmvs_loop_export_sizes(self.handle, C.byref(sz)))
+        out, buf = self._export_buffers(sz, device, arrays)
+        tab = self._index2image(index2image)
+        flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
+        _check(self.lib.pmvs_loop_export(self.handle, flags, _ptr(tab), C.byref(buf)))
+        return out
+
+    def export_patches(self, patches: np.ndarray, writer_order: bool = True, index2image=None, device: bool = False,
+                       arrays=None) -> dict:
+        """pmvs_export_patches: loop_export's arrays for caller-supplied PATCH_DTYPE records."""
+        pa = np.ascontiguousarray(patches, PATCH_DTYPE)
+        sz = ExportSizes()
+        _check(self.lib.pmvs_export_patches_sizes(self.handle, _ptr(pa), len(pa), C.byref(sz)))
+        out, buf = self._export_buffers(sz, device, arrays)
+        tab = self._index2image(index2image)
+        flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
+        _check(self.lib.pmvs_export_patches(self.handle, _ptr(pa), len(pa), flags, _ptr(tab), C.byref(buf)))
+        return out
 
     def patch_colors(self, coords: np.ndarray, images) -> np.ndarray:
         """writePLY colour mode 0 for patches (coords [n,4], images: list of view-index lists)."""

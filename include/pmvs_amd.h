@@ -333,6 +333,48 @@ pmvs_status pmvs_loop_fetch(pmvs_scene* scene, pmvs_patch* out, int32_t n);
  * (identical-repetition checks of a device-resident pipeline).  pmvs_loop_fetch still works after it. */
 pmvs_status pmvs_loop_hash(pmvs_scene* scene, uint64_t* hash);
 
+/* The model as the compact arrays the writers (pmvs_write_ply / _patches / _pset) and a downstream
+ * GPU stage read, produced on the device from the records where they lie: about 76 bytes per patch
+ * plus 4 per list entry of each list array cross PCIe instead of the 1608-byte record (and nothing in
+ * device mode).  Replaces CPatchOrganizerS::collectPatches(1) (patchOrganizerS.cpp:207-236: target images in
+ * order, their cells in raster order, each cell's list in insertion = model order, every patch at its
+ * first registration), the field and list gathers of writePatches2 (patchOrganizerS.cpp:89-132) and
+ * writePLY's colour mode 0 (patchOrganizerS.cpp:716-731).  Writer order: rows sorted by (lowest target
+ * index bt in images, cell grids[k0][1] * gwidth(bt) + grids[k0][0] at bt's first position k0), a patch
+ * without a target image last, equal keys in model order (a stable sort). */
+#define PMVS_EXPORT_WRITER_ORDER 1 /* rows in CPatchOrganizerS::collectPatches(1) order (what pmvs2 writes);
+                                      without it: model order, row i = record i of pmvs_loop_fetch */
+#define PMVS_EXPORT_DEVICE       2 /* every pointer in pmvs_export_buffers is a device pointer on the scene's device */
+
+typedef struct pmvs_export_sizes { int32_t patches, reserved; int64_t image_entries, vimage_entries; } pmvs_export_sizes;
+
+typedef struct pmvs_export_buffers {   /* any pointer may be NULL: that array is skipped */
+  float*   fields;      /* patches x 11: coord[4], normal[4], ncc, dscale, ascale (the writers' layout) */
+  int32_t* colors;      /* patches x 3: writePLY colour mode 0, exactly pmvs_patch_colors' values */
+  int64_t* image_off;   /* patches + 1 */
+  int32_t* image_ids;   /* image_entries: _images with index2image applied (identity when index2image == NULL) */
+  int32_t* image_idx;   /* image_entries: _images as view indexes */
+  int64_t* vimage_off;  /* patches + 1 */
+  int32_t* vimage_ids;  /* vimage_entries: _vimages with index2image applied */
+  int32_t* source;      /* patches: the model index of each output row */
+} pmvs_export_buffers;
+
+/* The pmvs_loop_* pair reads the result pmvs_run_loop left on the device (PMVS_EINVAL when there is
+ * none, as pmvs_loop_hash) and does not consume it: pmvs_loop_hash and pmvs_loop_fetch still work
+ * afterwards.  index2image: num_views image numbers on the host, or NULL.  Offsets are 64-bit (a
+ * C5-size model times its list lengths passes 2^31); zero patches give offsets {0}.  The work is queued
+ * on the scene's stream and the call returns after it has finished, so device-mode buffers are ready for
+ * any other stream.  A device-mode buffer has the size pmvs_*_export_sizes reported. */
+pmvs_status pmvs_loop_export_sizes(pmvs_scene* scene, pmvs_export_sizes* sizes);
+pmvs_status pmvs_loop_export(pmvs_scene* scene, int32_t flags, const int32_t* index2image,
+                             const pmvs_export_buffers* buffers);
+/* The same export of caller-supplied records (results of pmvs_filter_run / pmvs_expand_run, or hand-made
+ * ones): uploaded once; list counts (1..PMVS_MAX_IMAGES images, 0..PMVS_MAX_IMAGES vimages) and view
+ * indexes are validated as pmvs_filter_run does (PMVS_EINVAL). */
+pmvs_status pmvs_export_patches_sizes(pmvs_scene* scene, const pmvs_patch* patches, int32_t n, pmvs_export_sizes* sizes);
+pmvs_status pmvs_export_patches(pmvs_scene* scene, const pmvs_patch* patches, int32_t n, int32_t flags,
+                                const int32_t* index2image, const pmvs_export_buffers* buffers);
+
 /* The seed phase, PMVS3::CSeed::init + run (seed.cpp:11-107) at CPU 1: target images in the
  * reference's std::shuffle(mt19937(42)) order, cells in raster order, the feature points of every
  * view (points: num_points[0] of view 0, then view 1, ..., as pmvs_detect_features returns them)
