@@ -1,4 +1,4 @@
-// pmvs2_main.cpp -- the `pmvs2 prefix option_file [PATCH] [PSET]` executable (reference
+// pmvs2_main.cpp -- the `pmvs2 prefix option_file [PATCH] [PSET] [DEPTH]` executable (reference
 // source/pmvs.cpp:7-63 with CFindMatch::init / run / write, findMatch.cpp:30-224), driving the
 // MI355X-native core through its C-ABI (include/pmvs_amd.h).  A drop-in for the program
 // genOption's pmvs.sh calls (genOption.cpp:73): same arguments, same input tree
@@ -125,9 +125,11 @@ void usage(const char* argv0) {
             << "oimages  5  0 2 4 6 8 (enumeration)" << std::endl
             << "        -1  24 48 (range specification)" << std::endl
             << std::endl
-            << "[Optional export] PATCH PSET" << std::endl
+            << "[Optional export] PATCH PSET DEPTH" << std::endl
             << " i.e export patch and pset: prefix option_file PATCH PSET"
-            << " i.e export patch only: prefix option_file PATCH" << std::endl;
+            << " i.e export patch only: prefix option_file PATCH" << std::endl
+            << " DEPTH: every target image's depth map, one value per csize x csize cell, as" << std::endl
+            << "        models/option_file.depth.<8-digit image number>.pfm (0 = no patch)" << std::endl;
 }
 
 }  // namespace
@@ -140,10 +142,11 @@ int main(int argc, char* argv[]) {
   for (int i = 0; i < argc; ++i) std::cout << std::endl << argv[i];
   std::cout << std::endl;
   const std::string prefix = argv[1], option = argv[2];
-  bool export_patch = false, export_pset = false;
+  bool export_patch = false, export_pset = false, export_depth = false;
   for (int i = 3; i < argc; ++i) {
     if (std::string(argv[i]) == "PATCH") export_patch = true;
     if (std::string(argv[i]) == "PSET") export_pset = true;
+    if (std::string(argv[i]) == "DEPTH") export_depth = true;
   }
   const double t0 = now_s();
 
@@ -389,6 +392,22 @@ int main(int argc, char* argv[]) {
     CHECK("patch", pmvs_write_patches((out + ".patch").c_str(), nmodel, fields.data(), nimg.data(), ids.data(),
                                       nvimg.data(), vids.data()));
   if (export_pset) CHECK("pset", pmvs_write_pset((out + ".pset").c_str(), nmodel, fields.data()));
+  if (export_depth) {
+    // what each target image sees of the model just written (CFilter::setDepthMaps over it, on the
+    // device): the depth of the nearest patch per cell, one PFM per target image
+    std::vector<int32_t> dims((size_t)tnum * 2);
+    std::vector<int64_t> doff((size_t)tnum + 1);
+    CHECK("depth maps", pmvs_depth_map_layout(sc, dims.data(), doff.data()));
+    std::vector<float> depth((size_t)std::max<int64_t>(doff[tnum], 1));
+    pmvs_depthmap_buffers db{};
+    db.depth = depth.data();
+    CHECK("depth maps", pmvs_loop_depth_maps(sc, PMVS_EXPORT_WRITER_ORDER, &db));
+    for (int t = 0; t < tnum; ++t) {
+      char name[32];
+      std::snprintf(name, sizeof(name), ".depth.%08d.pfm", images[t]);
+      CHECK("pfm", pmvs_write_pfm((out + name).c_str(), dims[2 * t], dims[2 * t + 1], depth.data() + doff[t]));
+    }
+  }
   pmvs_scene_destroy(sc);
   pmvs_options_free(opt);
   const double t_end = now_s();

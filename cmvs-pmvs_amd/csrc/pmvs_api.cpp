@@ -1589,6 +1589,94 @@ pmvs_status pmvs_export_patches(pmvs_scene* sc, const pmvs_patch* patches, int32
   return export_records(sc, dP, n, sz, flags, index2image, buffers);
 }
 
+// ---- per-target depth maps (pmvs_depthmap.hip)
+namespace {
+// Target t's cell grid and the maps' cell offsets (tnum + 1 entries); returns the widest grid.
+int depth_map_layout(const pmvs_scene* sc, int32_t* dims, int64_t* offsets) {
+  int64_t off = 0;
+  int max_gwidth = 1;
+  for (int t = 0; t < sc->ds.tnum; ++t) {
+    const int gw = (sc->hviews[t].w[sc->ds.level] + sc->ds.csize - 1) / sc->ds.csize;
+    const int gh = (sc->hviews[t].h[sc->ds.level] + sc->ds.csize - 1) / sc->ds.csize;
+    if (dims) { dims[2 * t] = gw; dims[2 * t + 1] = gh; }
+    if (offsets) offsets[t] = off;
+    off += (int64_t)gw * gh;
+    max_gwidth = std::max(max_gwidth, gw);
+  }
+  if (offsets) offsets[sc->ds.tnum] = off;
+  return max_gwidth;
+}
+
+// The depth maps of the device records dP[0, n).
+pmvs_status depth_maps_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, int32_t flags, const pmvs_depthmap_buffers* b) {
+  const bool dev = (flags & PMVS_EXPORT_DEVICE) != 0;
+  if (!b->patch && !b->depth && !b->normal && !b->ncc) return PMVS_OK;
+  std::vector<int64_t> off((size_t)sc->ds.tnum + 1);
+  const int max_gwidth = depth_map_layout(sc, nullptr, off.data());
+  const size_t cells = (size_t)off.back();
+  static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "depth map array types");
+  ExportTemp tmp;
+  long long* d_off = nullptr;
+  int* d_src = nullptr;
+  EXPCHK(tmp.alloc(&d_off, off.size()));
+  EXPCHK(hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice, sc->stream));
+  if ((flags & PMVS_EXPORT_WRITER_ORDER) && n > 0) {  // the export's order, from the export's code
+    EXPCHK(tmp.alloc(&d_src, (size_t)n));
+    EXPCHK(export_order(sc->ds, dP, n, max_gwidth, d_src, nullptr, nullptr, sc->stream));
+  }
+  DepthMapArrays a;
+  if (dev) {  // straight into the caller's device buffers
+    a.patch = b->patch; a.depth = b->depth; a.normal = b->normal; a.ncc = b->ncc;
+  } else {    // device staging for the requested arrays
+    if (b->patch) EXPCHK(tmp.alloc(&a.patch, cells));
+    if (b->depth) EXPCHK(tmp.alloc(&a.depth, cells));
+    if (b->normal) EXPCHK(tmp.alloc(&a.normal, cells * 3));
+    if (b->ncc) EXPCHK(tmp.alloc(&a.ncc, cells));
+  }
+  EXPCHK(depth_map_pass(sc->ds, dP, n, d_src, d_off, (long long)cells, a, sc->stream));
+  if (!dev) {
+    auto down = [&](void* dst, const void* src, size_t bytes) {
+      return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sc->stream) : hipSuccess;
+    };
+    EXPCHK(down(b->patch, a.patch, cells * sizeof(int32_t)));
+    EXPCHK(down(b->depth, a.depth, cells * sizeof(float)));
+    EXPCHK(down(b->normal, a.normal, cells * 3 * sizeof(float)));
+    EXPCHK(down(b->ncc, a.ncc, cells * sizeof(float)));
+    EXPCHK(hipStreamSynchronize(sc->stream));
+  }
+  return PMVS_OK;
+}
+}  // namespace
+
+pmvs_status pmvs_depth_map_layout(pmvs_scene* sc, int32_t* dims, int64_t* offsets) {
+  if (!sc) return fail(PMVS_EINVAL, "invalid argument");
+  depth_map_layout(sc, dims, offsets);
+  return PMVS_OK;
+}
+
+pmvs_status pmvs_loop_depth_maps(pmvs_scene* sc, int32_t flags, const pmvs_depthmap_buffers* buffers) {
+  if (!sc || !buffers || (flags & ~(PMVS_EXPORT_WRITER_ORDER | PMVS_EXPORT_DEVICE))) return fail(PMVS_EINVAL, "invalid argument");
+  if (sc->lkept < 0) return fail(PMVS_EINVAL, "loop_depth_maps: no loop result on the device");
+  HIPCHK(hipSetDevice(sc->device));
+  return depth_maps_records(sc, sc->fpatches.p, sc->lkept, flags, buffers);
+}
+
+pmvs_status pmvs_depth_maps_patches(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, int32_t flags,
+                                    const pmvs_depthmap_buffers* buffers) {
+  if (!sc || !buffers || n < 0 || (n > 0 && !patches) || (flags & ~(PMVS_EXPORT_WRITER_ORDER | PMVS_EXPORT_DEVICE)))
+    return fail(PMVS_EINVAL, "invalid argument");
+  if (pmvs_status st = check_export_patches(sc, patches, n, nullptr)) return st;
+  HIPCHK(hipSetDevice(sc->device));
+  // a buffer of its own: sc->fpatches may hold a loop result
+  ExportTemp tmp;
+  pmvs_patch* dP = nullptr;
+  if (n) {
+    EXPCHK(tmp.alloc(&dP, (size_t)n));
+    EXPCHK(hipMemcpyAsync(dP, patches, (size_t)n * sizeof(pmvs_patch), hipMemcpyHostToDevice, sc->stream));
+  }
+  return depth_maps_records(sc, dP, n, flags, buffers);
+}
+
 pmvs_status pmvs_scene_set_shard(pmvs_scene* sc, int32_t rank, int32_t world, pmvs_allgather_fn fn, void* ctx) {
   if (!sc || world < 1 || rank < 0 || rank >= world || (world > 1 && !fn)) return fail(PMVS_EINVAL, "invalid shard");
   sc->shard_rank = rank;

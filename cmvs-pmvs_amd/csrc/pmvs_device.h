@@ -83,6 +83,17 @@ __device__ __forceinline__ void project(const DView& v, const float* c, int leve
   out[2] = v2;
 }
 
+// The depth maps of CFilter::setDepthMaps (filter.cpp:667-732): a cell holds the key
+// (depth_bits(depth) << 32) | patch, whose unsigned order is the depth's order (depth_bits is a
+// bijection of the f32 bit patterns), and a target's map has gwidth x gheight cells.
+__device__ __forceinline__ unsigned int depth_bits(float d) {
+  const unsigned int u = __float_as_uint(d);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float depth_of(const DView& v, const float* c) { return dot4(v.oaxis, c); }
+__device__ __forceinline__ int gwidth(const DScene& s, int t) { return (s.views[t].w[s.level] + s.csize - 1) / s.csize; }
+__device__ __forceinline__ int gheight(const DScene& s, int t) { return (s.views[t].h[s.level] + s.csize - 1) / s.csize; }
+
 // COptim::getUnit, optim.cpp:1116-1124.
 __device__ __forceinline__ float get_unit(const DScene& s, const DView& v, const float* coord) {
   const float d[4] = {coord[0] - v.center[0], coord[1] - v.center[1], coord[2] - v.center[2], coord[3] - v.center[3]};

@@ -56,7 +56,8 @@ __global__ __launch_bounds__(256) void export_sizes_kernel(const pmvs_patch* __r
 // cell term non-negative for any int16 grid entry and 2^cell_bits exceeds it, so the keys order as
 // (bt, cell) does; a record without a target image gets tnum << cell_bits and sorts last.
 // kKeyLanes lanes share a record: they read its images entries side by side and reduce
-// (index << 8 | position) with a minimum.  keys may be null (model order: counts only).
+// (index << 8 | position) with a minimum.  keys may be null (model order: counts only), and so may the
+// two count arrays (export_order for a caller that wants the order alone).
 __global__ __launch_bounds__(256) void export_key_kernel(DScene s, const pmvs_patch* __restrict__ P, int n, int cell_bits,
                                                          long long bias, unsigned long long* __restrict__ keys,
                                                          int* __restrict__ cnt_i, int* __restrict__ cnt_v) {
@@ -81,8 +82,8 @@ __global__ __launch_bounds__(256) void export_key_kernel(DScene s, const pmvs_pa
       best = o < best ? o : best;
     }
     if (live && sub == 0) {
-      cnt_i[i] = ni;
-      cnt_v[i] = clamp_count(q->num_vimages);
+      if (cnt_i) cnt_i[i] = ni;
+      if (cnt_v) cnt_v[i] = clamp_count(q->num_vimages);
       if (keys && best == INT_MAX) {
         keys[i] = (unsigned long long)s.tnum << cell_bits;
       } else if (keys) {
@@ -201,11 +202,40 @@ hipError_t export_sizes(const pmvs_patch* P, int n, unsigned long long* d_tot, h
   return hipGetLastError();
 }
 
+// The writer order of the records (the one place it is computed: export_pass and depth_map_pass call
+// this): export_key_kernel, then a stable radix sort of (key, model index) over the key bits in use.
+hipError_t export_order(const DScene& s, const pmvs_patch* P, int n, int max_gwidth, int* sorted, int* cnt_i, int* cnt_v,
+                        hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  // key layout (export_key_kernel): cell + bias below 2^cell_bits, the target index above
+  const long long bias = 32768LL * (max_gwidth + 1);
+  int cell_bits = 1, end_bit;
+  while ((1LL << cell_bits) < 2 * bias) ++cell_bits;
+  for (end_bit = cell_bits; ((long long)s.tnum >> (end_bit - cell_bits)) != 0; ++end_bit) {}
+  DevMem keys, keys2, idx, temp;
+  size_t tb_sort = 0;
+  XCHK(keys.alloc(n * sizeof(unsigned long long)));
+  XCHK(keys2.alloc(n * sizeof(unsigned long long)));
+  XCHK(idx.alloc(n * sizeof(int)));
+  XCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, keys.as<unsigned long long>(), keys2.as<unsigned long long>(),
+                                          idx.as<int>(), sorted, n, 0, end_bit, st));
+  XCHK(temp.alloc(tb_sort));
+  hipLaunchKernelGGL(export_key_kernel, dim3(grid_for(n, 256 / kKeyLanes)), dim3(256), 0, st, s, P, n, cell_bits, bias,
+                     keys.as<unsigned long long>(), cnt_i, cnt_v);
+  XCHK(hipGetLastError());
+  hipLaunchKernelGGL(export_iota_kernel, dim3(grid_for(n, 256)), dim3(256), 0, st, idx.as<int>(), n);
+  XCHK(hipGetLastError());
+  XCHK(hipcub::DeviceRadixSort::SortPairs(temp.p, tb_sort, keys.as<unsigned long long>(), keys2.as<unsigned long long>(),
+                                          idx.as<int>(), sorted, n, 0, end_bit, st));
+  // the scratch above is freed on return: the work that reads it must have finished
+  return hipStreamSynchronize(st);
+}
+
 hipError_t export_pass(const DScene& s, const pmvs_patch* P, int n, bool writer_order, int max_gwidth, const int* d_tab,
                        const ExportArrays& out, hipStream_t st) {
   if (n <= 0) return hipSuccess;
   const size_t n1 = (size_t)n + 1;
-  DevMem cnt_i, cnt_v, c64_i, c64_v, off_i, off_v, keys, keys2, idx, idx2, temp;
+  DevMem cnt_i, cnt_v, c64_i, c64_v, off_i, off_v, idx2, temp;
   XCHK(cnt_i.alloc(n * sizeof(int)));
   XCHK(cnt_v.alloc(n * sizeof(int)));
   XCHK(c64_i.alloc(n1 * sizeof(long long)));
@@ -219,37 +249,26 @@ hipError_t export_pass(const DScene& s, const pmvs_patch* P, int n, bool writer_
     XCHK(off_v.alloc(n1 * sizeof(long long)));
     voff = off_v.as<long long>();
   }
-  // key layout (export_key_kernel): cell + bias below 2^cell_bits, the target index above
-  const long long bias = 32768LL * (max_gwidth + 1);
-  int cell_bits = 1, end_bit;
-  while ((1LL << cell_bits) < 2 * bias) ++cell_bits;
-  for (end_bit = cell_bits; ((long long)s.tnum >> (end_bit - cell_bits)) != 0; ++end_bit) {}
-  size_t tb_sort = 0, tb_scan = 0;
+  size_t tb_scan = 0;
   const int* src = nullptr;
-  if (writer_order) {
-    XCHK(keys.alloc(n * sizeof(unsigned long long)));
-    XCHK(keys2.alloc(n * sizeof(unsigned long long)));
-    XCHK(idx.alloc(n * sizeof(int)));
-    if (!out.source) XCHK(idx2.alloc(n * sizeof(int)));
-    XCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, keys.as<unsigned long long>(), keys2.as<unsigned long long>(),
-                                            idx.as<int>(), idx.as<int>(), n, 0, end_bit, st));
-  }
   XCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_scan, c64_i.as<long long>(), ioff, (int)n1, st));
-  XCHK(temp.alloc(tb_sort > tb_scan ? tb_sort : tb_scan));
-
-  hipLaunchKernelGGL(export_key_kernel, dim3(grid_for(n, 256 / kKeyLanes)), dim3(256), 0, st, s, P, n, cell_bits, bias,
-                     writer_order ? keys.as<unsigned long long>() : nullptr, cnt_i.as<int>(), cnt_v.as<int>());
-  XCHK(hipGetLastError());
+  XCHK(temp.alloc(tb_scan));
   if (writer_order) {
-    int* sorted = out.source ? out.source : idx2.as<int>();
-    hipLaunchKernelGGL(export_iota_kernel, dim3(grid_for(n, 256)), dim3(256), 0, st, idx.as<int>(), n);
-    XCHK(hipGetLastError());
-    XCHK(hipcub::DeviceRadixSort::SortPairs(temp.p, tb_sort, keys.as<unsigned long long>(), keys2.as<unsigned long long>(),
-                                            idx.as<int>(), sorted, n, 0, end_bit, st));
+    int* sorted = out.source;
+    if (!sorted) {
+      XCHK(idx2.alloc(n * sizeof(int)));
+      sorted = idx2.as<int>();
+    }
+    XCHK(export_order(s, P, n, max_gwidth, sorted, cnt_i.as<int>(), cnt_v.as<int>(), st));
     src = sorted;
-  } else if (out.source) {
-    hipLaunchKernelGGL(export_iota_kernel, dim3(grid_for(n, 256)), dim3(256), 0, st, out.source, n);
+  } else {  // model order: the counts only
+    hipLaunchKernelGGL(export_key_kernel, dim3(grid_for(n, 256 / kKeyLanes)), dim3(256), 0, st, s, P, n, 0, 0LL,
+                       (unsigned long long*)nullptr, cnt_i.as<int>(), cnt_v.as<int>());
     XCHK(hipGetLastError());
+    if (out.source) {
+      hipLaunchKernelGGL(export_iota_kernel, dim3(grid_for(n, 256)), dim3(256), 0, st, out.source, n);
+      XCHK(hipGetLastError());
+    }
   }
   hipLaunchKernelGGL(export_counts_kernel, dim3(grid_for((long long)n1, 256)), dim3(256), 0, st, src, cnt_i.as<int>(),
                      cnt_v.as<int>(), n, c64_i.as<long long>(), c64_v.as<long long>());

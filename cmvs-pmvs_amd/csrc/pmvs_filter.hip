@@ -215,17 +215,11 @@ struct QuadJobs {
 };
 
 // --------------------------------------------------------------------------- small helpers
-__device__ __forceinline__ unsigned int depth_bits(float d) {
-  const unsigned int u = __float_as_uint(d);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float depth_of(const DView& v, const float* c) { return dot4(v.oaxis, c); }
+// depth_bits, depth_of, gwidth and gheight are in pmvs_device.h (pmvs_depthmap.hip shares them).
 __device__ __forceinline__ bool in_grid(const DScene& s, int t, int ix, int iy) {
   return 0 <= ix && ix < (s.views[t].w[s.level] + s.csize - 1) / s.csize && 0 <= iy &&
          iy < (s.views[t].h[s.level] + s.csize - 1) / s.csize;
 }
-__device__ __forceinline__ int gwidth(const DScene& s, int t) { return (s.views[t].w[s.level] + s.csize - 1) / s.csize; }
-__device__ __forceinline__ int gheight(const DScene& s, int t) { return (s.views[t].h[s.level] + s.csize - 1) / s.csize; }
 
 // CFindMatch::isNeighbor / isNeighborRadius (findMatch.cpp:125-185).
 template <class PL, class PR>

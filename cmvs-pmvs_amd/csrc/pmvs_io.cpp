@@ -657,4 +657,23 @@ pmvs_status pmvs_write_ply(const char* path, int32_t n, const float* fields, con
   return ofstr.good() ? PMVS_OK : pmvs_io_fail(PMVS_EINVAL, "write failed: %s", path);
 }
 
+// One-channel PFM: a negative scale says little-endian, and the rows go bottom to top.
+pmvs_status pmvs_write_pfm(const char* path, int32_t width, int32_t height, const float* data) {
+  if (!path || !data || width <= 0 || height <= 0) return pmvs_io_fail(PMVS_EINVAL, "invalid argument");
+  std::ofstream ofstr(path, std::ios::binary);
+  if (!ofstr.is_open()) return pmvs_io_fail(PMVS_EINVAL, "cannot write %s", path);
+  ofstr << "Pf\n" << width << ' ' << height << "\n-1.0\n";
+  std::vector<char> row((size_t)width * 4);
+  for (int y = height - 1; y >= 0; --y) {
+    const float* src = data + (size_t)y * width;
+    for (int x = 0; x < width; ++x) {
+      uint32_t u;
+      std::memcpy(&u, src + x, 4);
+      for (int k = 0; k < 4; ++k) row[(size_t)4 * x + k] = (char)((u >> (8 * k)) & 0xff);
+    }
+    ofstr.write(row.data(), (std::streamsize)row.size());
+  }
+  return ofstr.good() ? PMVS_OK : pmvs_io_fail(PMVS_EINVAL, "write failed: %s", path);
+}
+
 }  // extern "C"

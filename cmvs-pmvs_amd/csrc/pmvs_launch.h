@@ -83,6 +83,23 @@ hipError_t export_sizes(const pmvs_patch* P, int n, unsigned long long* d_tot, h
 // its scratch cannot be allocated.
 hipError_t export_pass(const DScene& s, const pmvs_patch* P, int n, bool writer_order, int max_gwidth, const int* d_tab,
                        const ExportArrays& out, hipStream_t st);
+// The writer order alone: sorted[r] = the model index of row r in collectPatches(1) order (n device
+// ints).  cnt_i / cnt_v (n device ints each, or null) receive the records' clamped list lengths.
+// Returns after the stream has finished the work.
+hipError_t export_order(const DScene& s, const pmvs_patch* P, int n, int max_gwidth, int* sorted, int* cnt_i, int* cnt_v,
+                        hipStream_t st);
+
+// ---- per-target depth maps (pmvs_depthmap.hip)
+// Device pointers of the arrays of pmvs_depthmap_buffers (include/pmvs_amd.h); null = not wanted.
+struct DepthMapArrays {
+  int* patch = nullptr;
+  float *depth = nullptr, *normal = nullptr, *ncc = nullptr;
+};
+// setDepthMaps over the records P[0, n) in model order (src null) or with row r = record src[r]:
+// d_off = the tnum + 1 cell offsets of the targets' maps on the device, cells = their total.  Returns
+// after the stream has finished the work; hipErrorOutOfMemory when its scratch cannot be allocated.
+hipError_t depth_map_pass(const DScene& s, const pmvs_patch* P, int n, const int* src, const long long* d_off,
+                          long long cells, const DepthMapArrays& out, hipStream_t st);
 
 // ---- filter pass (pmvs_filter.hip)
 // Page-locked host staging (hipHostMalloc), grown on demand: the large per-pass downloads

@@ -115,6 +115,10 @@ class ExportBuffers(C.Structure):  # pmvs_export_buffers
 EXPORT_WRITER_ORDER, EXPORT_DEVICE = 1, 2
 
 
+class DepthMapBuffers(C.Structure):  # pmvs_depthmap_buffers
+    _fields_ = [(k, C.c_void_p) for k in ("patch", "depth", "normal", "ncc")]
+
+
 class SeedStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("trial", "pass_", "fail0", "fail1", "refined", "rounds", "candidates",
                                           "reserved")] + [(k, C.c_double) for k in ("wall_ms", "gen_ms", "refine_ms")]
@@ -158,6 +162,7 @@ EXPORTS = ["pmvs_last_error", "pmvs_device_count", "pmvs_scene_create", "pmvs_sc
            "pmvs_write_ply", "pmvs_patch_colors", "pmvs_filter_run",
            "pmvs_expand_run", "pmvs_expand_fetch", "pmvs_run_loop", "pmvs_loop_fetch", "pmvs_loop_hash",
            "pmvs_loop_export_sizes", "pmvs_loop_export", "pmvs_export_patches_sizes", "pmvs_export_patches",
+           "pmvs_depth_map_layout", "pmvs_loop_depth_maps", "pmvs_depth_maps_patches", "pmvs_write_pfm",
            "pmvs_scene_set_shard", "pmvs_scene_set_shard_rccl", "pmvs_scene_set_cluster",
            "pmvs_scene_set_cluster_rccl", "pmvs_rccl_unique_id",
            "pmvs_rccl_create", "pmvs_rccl_destroy", "pmvs_rccl_allgather", "pmvs_rccl_allgather_device",
@@ -229,6 +234,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.pmvs_export_patches_sizes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(ExportSizes)]
     lib.pmvs_export_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                         C.POINTER(ExportBuffers)]
+    lib.pmvs_depth_map_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pmvs_loop_depth_maps.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DepthMapBuffers)]
+    lib.pmvs_depth_maps_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DepthMapBuffers)]
+    lib.pmvs_write_pfm.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.pmvs_scene_set_shard.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.pmvs_scene_set_cluster.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pmvs_scene_set_cluster_rccl.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
@@ -611,6 +620,57 @@ class Scene:
         _check(self.lib.pmvs_export_patches(self.handle, _ptr(pa), len(pa), flags, _ptr(tab), C.byref(buf)))
         return out
 
+    # pmvs_depthmap_buffers: array name -> (dtype, shape from the number of cells)
+    DEPTH_MAP_ARRAYS = {"patch": ("int32", lambda c: (c,)), "depth": ("float32", lambda c: (c,)),
+                        "normal": ("float32", lambda c: (c, 3)), "ncc": ("float32", lambda c: (c,))}
+
+    def depth_map_layout(self):
+        """pmvs_depth_map_layout: (dims [T, 2] int32 = every target's (gwidth, gheight), offsets [T + 1]
+        int64 = the first cell of every target's map, the last entry the total)."""
+        tnum = self.desc.num_targets
+        dims, off = np.zeros((tnum, 2), np.int32), np.zeros(tnum + 1, np.int64)
+        _check(self.lib.pmvs_depth_map_layout(self.handle, _ptr(dims), _ptr(off)))
+        return dims, off
+
+    def _depth_map_buffers(self, device: bool, arrays):
+        """The arrays of one depth-map call and the pmvs_depthmap_buffers that points at them, by
+        _export_buffers' conventions."""
+        cells = int(self.depth_map_layout()[1][-1])
+        names = list(self.DEPTH_MAP_ARRAYS) if arrays is None else list(arrays)
+        out, buf = {}, DepthMapBuffers()
+        for k in names:
+            dt, shape = self.DEPTH_MAP_ARRAYS[k]
+            if device:
+                import torch
+                out[k] = torch.empty(shape(cells), dtype=getattr(torch, dt), device=torch.device("cuda", self.device))
+                setattr(buf, k, out[k].data_ptr() if out[k].numel() else None)
+            else:
+                out[k] = np.empty(shape(cells), dt)
+                setattr(buf, k, out[k].ctypes.data if out[k].size else None)
+        return out, buf
+
+    def loop_depth_maps(self, writer_order: bool = True, device: bool = False, arrays=None) -> dict:
+        """pmvs_loop_depth_maps: what every target image sees of the last run_loop(fetch=False) result
+        (CFilter::setDepthMaps over it), keyed by the fields of pmvs_depthmap_buffers: patch [cells]
+        (-1 = empty), depth [cells], normal [cells, 3], ncc [cells]; depth_map_layout() gives the
+        cells of each target and depth_map_view one target's image.  `patch` indexes the rows of
+        loop_export(writer_order=...) (model order: the records of loop_fetch).  Does not consume the
+        result.  device=True: torch tensors on the scene's device, written there.  arrays: the names
+        wanted (None = all)."""
+        out, buf = self._depth_map_buffers(device, arrays)
+        flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
+        _check(self.lib.pmvs_loop_depth_maps(self.handle, flags, C.byref(buf)))
+        return out
+
+    def depth_maps_patches(self, patches: np.ndarray, writer_order: bool = True, device: bool = False,
+                           arrays=None) -> dict:
+        """pmvs_depth_maps_patches: loop_depth_maps' arrays for caller-supplied PATCH_DTYPE records."""
+        pa = np.ascontiguousarray(patches, PATCH_DTYPE)
+        out, buf = self._depth_map_buffers(device, arrays)
+        flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
+        _check(self.lib.pmvs_depth_maps_patches(self.handle, _ptr(pa), len(pa), flags, C.byref(buf)))
+        return out
+
     def patch_colors(self, coords: np.ndarray, images) -> np.ndarray:
         """writePLY colour mode 0 for patches (coords [n,4], images: list of view-index lists)."""
         coords = np.ascontiguousarray(coords, np.float32).reshape(-1, 4)
@@ -754,6 +814,22 @@ def write_ply(path: str, fields, colors):
     f = np.ascontiguousarray(fields, np.float32).reshape(-1, 11)
     c = np.ascontiguousarray(colors, np.int32).reshape(-1, 3)
     _check(load_library().pmvs_write_ply(path.encode(), len(f), _ptr(f), _ptr(c)))
+
+
+def write_pfm(path: str, data):
+    """pmvs_write_pfm: a [height, width] float32 image (top row first) as a one-channel PFM."""
+    a = np.ascontiguousarray(data, np.float32)
+    if a.ndim != 2:
+        raise ValueError("write_pfm takes a [height, width] array")
+    _check(load_library().pmvs_write_pfm(path.encode(), a.shape[1], a.shape[0], _ptr(a)))
+
+
+def depth_map_view(array, dims, offsets, t: int):
+    """Target t's (gheight, gwidth[, 3]) view of an array of loop_depth_maps / depth_maps_patches
+    (numpy or torch), dims and offsets from depth_map_layout()."""
+    gw, gh = int(dims[t][0]), int(dims[t][1])
+    part = array[int(offsets[t]):int(offsets[t + 1])]
+    return part.reshape((gh, gw) + tuple(part.shape[1:]))
 
 
 def patches_from_refined(refined: np.ndarray) -> np.ndarray:

@@ -375,6 +375,42 @@ pmvs_status pmvs_export_patches_sizes(pmvs_scene* scene, const pmvs_patch* patch
 pmvs_status pmvs_export_patches(pmvs_scene* scene, const pmvs_patch* patches, int32_t n, int32_t flags,
                                 const int32_t* index2image, const pmvs_export_buffers* buffers);
 
+/* What each target image sees of the model: CFilter::setDepthMaps (filter.cpp:667-732) over the rows of
+ * an export, produced on the device.  Every row is projected into every target image at the scene's
+ * level and touches the up to four cells {floor, ceil}(x / csize) x {floor, ceil}(y / csize) that lie
+ * in the target's gwidth x gheight cell grid; a cell keeps the row with the smallest depth
+ * (OpticalAxis * coord, the f32 value setDepthMapsThread compares) and, at equal depths, the earlier
+ * row (the reference replaces only when `depth < dtmp`).  One cell per csize x csize pixels is the
+ * density PMVS reconstructs at.
+ * Layout: target t's map is row-major, gheight(t) rows of gwidth(t) cells, and starts at cell
+ * offsets[t] of every array; targets in index order; offsets[num_targets] cells in all.
+ * Rows: flags are PMVS_EXPORT_WRITER_ORDER and PMVS_EXPORT_DEVICE and no other bit (PMVS_EINVAL).
+ * Without WRITER_ORDER row i is record i (model order); with it the rows are those of
+ * pmvs_loop_export / pmvs_export_patches(PMVS_EXPORT_WRITER_ORDER) of the same records -- the order comes
+ * from the same code -- so `patch` indexes that export's arrays, and the maps are what the reference's
+ * setDepthMaps computes over the model it writes.  With PMVS_EXPORT_DEVICE every pointer is a device
+ * pointer on the scene's device. */
+typedef struct pmvs_depthmap_buffers {  /* any pointer may be NULL: that array is skipped */
+  int32_t* patch;   /* cells: row of the winning patch, -1 = empty cell */
+  float*   depth;   /* cells: OpticalAxis * coord of the winner (the value setDepthMaps compares); 0 = empty */
+  float*   normal;  /* cells x 3: the winner's normal x, y, z; 0 = empty */
+  float*   ncc;     /* cells: the winner's ncc; 0 = empty */
+} pmvs_depthmap_buffers;
+
+/* dims: num_targets x 2 (gwidth, gheight); offsets: num_targets + 1 (first cell of each target's map;
+ * the last entry is the total).  Host arrays; either may be NULL.  Depends on the scene only. */
+pmvs_status pmvs_depth_map_layout(pmvs_scene* scene, int32_t* dims, int64_t* offsets);
+/* The maps of the result pmvs_run_loop left on the device (PMVS_EINVAL when there is none).  Reads it
+ * where it lies and does not consume it: pmvs_loop_hash, pmvs_loop_fetch and pmvs_loop_export still
+ * work afterwards.  Scratch (8 bytes per cell, 16 or 32 per row) is allocated for the call and freed on
+ * return.  The work is queued on the scene's stream and the call returns after it has finished, so
+ * device-mode buffers are ready for any other stream. */
+pmvs_status pmvs_loop_depth_maps(pmvs_scene* scene, int32_t flags, const pmvs_depthmap_buffers* buffers);
+/* The same for caller-supplied records: uploaded once and validated as pmvs_export_patches validates
+ * them (PMVS_EINVAL).  n = 0 gives all-empty maps. */
+pmvs_status pmvs_depth_maps_patches(pmvs_scene* scene, const pmvs_patch* patches, int32_t n, int32_t flags,
+                                    const pmvs_depthmap_buffers* buffers);
+
 /* The seed phase, PMVS3::CSeed::init + run (seed.cpp:11-107) at CPU 1: target images in the
  * reference's std::shuffle(mt19937(42)) order, cells in raster order, the feature points of every
  * view (points: num_points[0] of view 0, then view 1, ..., as pmvs_detect_features returns them)
@@ -513,6 +549,11 @@ pmvs_status pmvs_write_patches(const char* path, int32_t n, const float* fields,
 pmvs_status pmvs_write_pset(const char* path, int32_t n, const float* fields);
 /* ASCII .ply with colour and quality (CPatchOrganizerS::writePLY, patchOrganizerS.cpp:687-776). */
 pmvs_status pmvs_write_ply(const char* path, int32_t n, const float* fields, const int32_t* colors);
+/* A one-channel PFM image of width x height floats given top row first (one target's `depth` map of
+ * pmvs_loop_depth_maps, width = gwidth, height = gheight): the header "Pf\n<width> <height>\n-1.0\n",
+ * then the rows from the bottom one to the top one as little-endian float32.  PMVS_EINVAL for a NULL
+ * argument, a non-positive size or a file that cannot be written. */
+pmvs_status pmvs_write_pfm(const char* path, int32_t width, int32_t height, const float* data);
 /* writePLY colour mode 0 on the device: mean of CPhotoSetS::getColor over the patch's images at
  * the scene level, floor(c + 0.5) clamped to 255.  images_flat holds nimg[i] view indexes per patch. */
 pmvs_status pmvs_patch_colors(pmvs_scene* scene, int32_t n, const float* coords4, const int32_t* nimg,
