@@ -34,25 +34,35 @@ namespace pmvsdev {
 #define REFINE_TSLOTS 48
 #endif
 
+typedef uint16_t img_t;       // an image index in LDS (a scene has at most 32767 views: pmvs_scene_create)
+
 template <int WS>
 struct WaveLds {
   static constexpr int S = WS * WS;
-  float tex[TEXCAP][S][4];  // RGB(+pad) per sample, sample-major like the reference vector
+  static constexpr int TP = (3 * S + 3) & ~3;  // a texture's 3 * S floats padded to 16 B (float4 reads)
+  static constexpr int F4 = 3 * S / 4;         // its whole float4s: 3 * S = 4 * F4 + 3 (S = 1 mod 4)
+  static_assert(3 * S == 4 * F4 + 3, "tex_dot / normalize read F4 float4s and a 3-float tail");
+  union {
+    alignas(16) float tex[TEXCAP][TP];  // RGB per sample, sample-major like the reference vector
+    float rays[PMVS_MAX_IMAGES][4];     // sort_images / check_angles (pre): no texture is live by then
+  };
   float ave[TEXCAP][4];     // per-texture channel means and ave2
   int valid[TEXCAP];
   int jview[TEXCAP], jlevel[TEXCAP];
   float jrow[TEXCAP][WS][2], jdx[TEXCAP][2], jdy[TEXCAP][2];  // jrow: each sample row's start (left)
   float res[TEXCAP];        // per-texture result (inccs)
-  int images[PMVS_MAX_IMAGES];
-  int nimg;
-  int list2[PMVS_MAX_IMAGES];
+  img_t images[PMVS_MAX_IMAGES];
+  img_t list2[PMVS_MAX_IMAGES];
   float fl[PMVS_MAX_IMAGES];
-  float fl2[PMVS_MAX_IMAGES];
-  float rays[PMVS_MAX_IMAGES][4];
-  int grids[PMVS_MAX_IMAGES][2];
+  float sc[2];              // setScales' dscale, ascale (lane 0 -> wave)
+  int nimg;
   int cand;
   int overflow;
 };
+// LDS budget: pre / post / filter_refimage run 12 single-wave workgroups per CU (3 waves per SIMD), so
+// a workgroup may take 163840 / 12 = 13653 B; 12800 B leaves the allocation granule's rounding inside
+// it.  WS = 9 cannot fit (its 16 textures alone are 15.6 KB) and stays at 2 waves per SIMD.
+static_assert(sizeof(WaveLds<7>) <= 12800 && sizeof(WaveLds<5>) <= 12800, "WaveLds: 12 workgroups per CU at wsize <= 7");
 
 // Order-preserving compaction across the wave: returns the position of this lane's kept element
 // among kept elements of lanes < lane, and writes the number kept to *count.
@@ -64,13 +74,14 @@ __device__ __forceinline__ int ballot_prefix(bool keep, int* count) {
 }
 
 // ---------------------------------------------------------------- texture batch
-// Grabs cnt (<= TEXCAP) textures: view jv(j) into LDS slot js(j), j < cnt, at the wave-uniform
+// Grabs cnt (<= TEXCAP) textures: view views[j] into LDS slot slot0 + j, j < cnt, at the wave-uniform
 // geometry (coord, px, py, normal); normalises the valid ones.  lds.valid[slot] is set.
-template <int WS>
-__device__ void grab_batch(const DScene& s, WaveLds<WS>& L, int cnt, const int* views, int slot0,
+template <int WS, typename IT>
+__device__ void grab_batch(const DScene& s, WaveLds<WS>& L, int cnt, const IT* views, int slot0,
                            const float* coord, const float* px, const float* py, const float* pz,
                            unsigned long long* grabs) {
   constexpr int S = WS * WS;
+  constexpr int F4 = WaveLds<WS>::F4;
   const int lane = lane_id();
   // --- per-texture setup (grabTex lines 818-846), one lane per texture
   if (lane < cnt) {
@@ -182,9 +193,9 @@ __device__ void grab_batch(const DScene& s, WaveLds<WS>& L, int cnt, const int* 
       r += (float)(a1[q] & 0xff) * f10 + (float)(b1[q] & 0xff) * f11;
       g += (float)((a1[q] >> 8) & 0xff) * f10 + (float)((b1[q] >> 8) & 0xff) * f11;
       b += (float)((a1[q] >> 16) & 0xff) * f10 + (float)((b1[q] >> 16) & 0xff) * f11;
-      L.tex[slot][k][0] = r;
-      L.tex[slot][k][1] = g;
-      L.tex[slot][k][2] = b;
+      L.tex[slot][3 * k + 0] = r;
+      L.tex[slot][3 * k + 1] = g;
+      L.tex[slot][3 * k + 2] = b;
     }
   }
   __syncthreads();
@@ -192,20 +203,40 @@ __device__ void grab_batch(const DScene& s, WaveLds<WS>& L, int cnt, const int* 
   if (lane < cnt) {
     const int slot = slot0 + lane;
     if (L.valid[slot]) {
+      // three float4s hold four samples (r g b r | g b r g | b r g b); every channel's sum still runs
+      // over the samples in order
+      const float4* T = reinterpret_cast<const float4*>(L.tex[slot]);
       float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
-      #pragma unroll 7  // a bounded unroll: the full 49-step one held every texel in registers (pre / post spilled)
-      for (int i = 0; i < S; ++i) {
-        const float4 q = *reinterpret_cast<const float4*>(L.tex[slot][i]);
-        a0 += q.x; a1 += q.y; a2 += q.z;
+      #pragma unroll 2  // a bounded unroll: the full one held every texel in registers (pre / post spilled)
+      for (int i = 0; i < F4; i += 3) {
+        const float4 u = T[i], v = T[i + 1], w = T[i + 2];
+        a0 += u.x; a1 += u.y; a2 += u.z;
+        a0 += u.w; a1 += v.x; a2 += v.y;
+        a0 += v.z; a1 += v.w; a2 += w.x;
+        a0 += w.y; a1 += w.z; a2 += w.w;
+      }
+      {
+        const float4 u = T[F4];  // the last sample (u.w is padding)
+        a0 += u.x; a1 += u.y; a2 += u.z;
       }
       const float fs3 = (float)S;
       a0 = __fdiv_rn(a0, fs3); a1 = __fdiv_rn(a1, fs3); a2 = __fdiv_rn(a2, fs3);
       float ave2 = 0.0f;
-      #pragma unroll 7
-      for (int i = 0; i < S; ++i) {
-        const float4 q = *reinterpret_cast<const float4*>(L.tex[slot][i]);
-        const float f0 = a0 - q.x, f1 = a1 - q.y, f2 = a2 - q.z;
+      const auto sq = [&](float r, float g, float b) {
+        const float f0 = a0 - r, f1 = a1 - g, f2 = a2 - b;
         ave2 += f0 * f0 + f1 * f1 + f2 * f2;
+      };
+      #pragma unroll 2
+      for (int i = 0; i < F4; i += 3) {
+        const float4 u = T[i], v = T[i + 1], w = T[i + 2];
+        sq(u.x, u.y, u.z);
+        sq(u.w, v.x, v.y);
+        sq(v.z, v.w, w.x);
+        sq(w.y, w.z, w.w);
+      }
+      {
+        const float4 u = T[F4];
+        sq(u.x, u.y, u.z);
       }
       ave2 = fsqrt_rn(__fdiv_rn(ave2, (float)(3 * S)));
       if (ave2 == 0.0f) ave2 = 1.0f;
@@ -218,9 +249,9 @@ __device__ void grab_batch(const DScene& s, WaveLds<WS>& L, int cnt, const int* 
     const int slot = slot0 + j;
     if (!L.valid[slot]) continue;
     const float a2 = L.ave[slot][3];
-    L.tex[slot][k][0] = __fdiv_rn(L.tex[slot][k][0] - L.ave[slot][0], a2);
-    L.tex[slot][k][1] = __fdiv_rn(L.tex[slot][k][1] - L.ave[slot][1], a2);
-    L.tex[slot][k][2] = __fdiv_rn(L.tex[slot][k][2] - L.ave[slot][2], a2);
+    L.tex[slot][3 * k + 0] = __fdiv_rn(L.tex[slot][3 * k + 0] - L.ave[slot][0], a2);
+    L.tex[slot][3 * k + 1] = __fdiv_rn(L.tex[slot][3 * k + 1] - L.ave[slot][1], a2);
+    L.tex[slot][3 * k + 2] = __fdiv_rn(L.tex[slot][3 * k + 2] - L.ave[slot][2], a2);
   }
   __syncthreads();
 }
@@ -229,15 +260,22 @@ __device__ void grab_batch(const DScene& s, WaveLds<WS>& L, int cnt, const int* 
 template <int WS>
 __device__ __forceinline__ float tex_dot(const WaveLds<WS>& L, int a, int b) {
   constexpr int S = WS * WS;
+  constexpr int F4 = WaveLds<WS>::F4;
+  const float4* A = reinterpret_cast<const float4*>(L.tex[a]);
+  const float4* B = reinterpret_cast<const float4*>(L.tex[b]);
   float ans = 0.0f;
-  #pragma unroll 7
-  for (int i = 0; i < S; ++i) {
-    const float4 p = *reinterpret_cast<const float4*>(L.tex[a][i]);
-    const float4 q = *reinterpret_cast<const float4*>(L.tex[b][i]);
+  #pragma unroll 6
+  for (int i = 0; i < F4; ++i) {
+    const float4 p = A[i], q = B[i];
     ans += p.x * q.x;
     ans += p.y * q.y;
     ans += p.z * q.z;
+    ans += p.w * q.w;
   }
+  const float4 p = A[F4], q = B[F4];  // the last sample (.w is padding)
+  ans += p.x * q.x;
+  ans += p.y * q.y;
+  ans += p.z * q.z;
   return __fdiv_rn(ans, (float)(3 * S));
 }
 
@@ -299,40 +337,6 @@ __device__ double my_f(const DScene& s, WaveLds<WS>& L, const RefineSetup& R, co
   return ret;
 }
 
-// COptim::computeINCC (weighted, robust), optim.cpp:865-938.  weights in L.fl2[].
-template <int WS>
-__device__ double compute_incc(const DScene& s, WaveLds<WS>& L, const float* coord, const float* normal,
-                               const int* idx, int nidx, unsigned long long* grabs) {
-  if (nidx < 2) return 2.0;
-  float px[4], py[4];
-  get_paxes(s, s.views[idx[0]], coord, normal, px, py);
-  const int size = imin(s.tau, nidx);
-  grab_batch<WS>(s, L, size, idx, 0, coord, px, py, normal, grabs);
-  const int lane = lane_id();
-  if (lane >= 1 && lane < size) {
-    float r = 0.0f;
-    if (L.valid[0] && L.valid[lane]) r = robustincc((float)(1.0 - (double)tex_dot<WS>(L, 0, lane)));
-    L.res[lane] = r;
-  }
-  __syncthreads();
-  double score = 0.0;
-  if (!L.valid[0]) {
-    score = 2.0;
-  } else {
-    float totalweight = 0.0f;
-    for (int i = 1; i < size; ++i) {
-      if (L.valid[i]) {
-        totalweight += L.fl2[i];
-        score += (double)(L.res[i] * L.fl2[i]);
-      }
-    }
-    if (totalweight == 0.0f) score = 2.0;
-    else score /= (double)totalweight;
-  }
-  __syncthreads();
-  return score;
-}
-
 // ---------------------------------------------------------------- image-list steps
 // COptim::addImages, optim.cpp:398-444.  Appends in visdata2 order.
 template <int WS>
@@ -391,6 +395,7 @@ __device__ void constraint_images(const DScene& s, WaveLds<WS>& L, const float* 
   for (int b = 1; b < n; b += TEXCAP - 1) {
     const int cnt = imin(TEXCAP - 1, n - b);
     if (ok0) grab_batch<WS>(s, L, cnt, L.images + b, 1, coord, px, py, normal, grabs);
+    else if (lane == 0) *grabs += (unsigned long long)cnt;  // setINCCs grabs them all the same: charged, not done
     if (lane < cnt) {
       float incc = 2.0f;
       if (ok0 && L.valid[1 + lane]) incc = 1.0f - tex_dot<WS>(L, 0, 1 + lane);
@@ -479,7 +484,7 @@ __device__ void sort_images(const DScene& s, WaveLds<WS>& L, const float* coord,
 }
 
 // CPatchOrganizerS::setScales, patchOrganizerS.cpp:663-684 (lane 0).
-__device__ void set_scales(const DScene& s, const int* images, int nimg, const float* coord, float* dscale, float* ascale) {
+__device__ void set_scales(const DScene& s, const img_t* images, int nimg, const float* coord, float* dscale, float* ascale) {
   const DView& v0 = s.views[images[0]];
   const float unit = get_unit(s, v0, coord);
   const float unit2 = 2.0f * unit;
@@ -564,19 +569,6 @@ __device__ void filter_images_by_angle(const DScene& s, WaveLds<WS>& L, const fl
   __syncthreads();
 }
 
-// CPatchOrganizerS::setGrids, patchOrganizerS.cpp:410-419.
-template <int WS>
-__device__ void set_grids(const DScene& s, WaveLds<WS>& L, const float* coord) {
-  const int lane = lane_id();
-  for (int k = lane; k < L.nimg; k += WAVE) {
-    float ic[3];
-    project(s.views[L.images[k]], coord, s.level, ic);
-    L.grids[k][0] = ((int)floorf(ic[0] + 0.5f)) / s.csize;
-    L.grids[k][1] = ((int)floorf(ic[1] + 0.5f)) / s.csize;
-  }
-  __syncthreads();
-}
-
 // COptim::setRefImage, optim.cpp:208-254, with setINCCs (pairwise, robust) optim.cpp:746-781.
 // The m x m INCC matrix lives in this workgroup's global scratch slot.
 template <int WS>
@@ -618,12 +610,16 @@ __device__ void set_ref_image(const DScene& s, WaveLds<WS>& L, const float* coor
       }
     }
   } else {
+    // blocks of B textures are grabbed once per block pair; the reference's setINCCs grabs each of the
+    // m textures once, and that is what is charged
+    unsigned long long regrabs = 0;
+    if (lane == 0) *grabs += (unsigned long long)m;
     for (int bi = 0; bi < m; bi += B) {
       const int ci = imin(B, m - bi);
-      grab_batch<WS>(s, L, ci, L.list2 + bi, 0, coord, px, py, normal, grabs);
+      grab_batch<WS>(s, L, ci, L.list2 + bi, 0, coord, px, py, normal, &regrabs);
       for (int bj = bi; bj < m; bj += B) {
         const int cj = imin(B, m - bj);
-        if (bj != bi) grab_batch<WS>(s, L, cj, L.list2 + bj, B, coord, px, py, normal, grabs);
+        if (bj != bi) grab_batch<WS>(s, L, cj, L.list2 + bj, B, coord, px, py, normal, &regrabs);
         const int np = (bj == bi) ? ci * (ci - 1) / 2 : ci * cj;
         for (int base = 0; base < np; base += WAVE) {
           const int p = base + lane;
@@ -711,11 +707,11 @@ __device__ void pre_candidate(const DScene& s, WaveLds<WS>& L, const pmvs_candid
     if (lane == 0 && L.nimg > 0) {
       float ds = dscale, as = 0.0f;
       set_scales(s, L.images, L.nimg, coord, &ds, &as);
-      L.fl2[0] = ds;
-      L.fl2[1] = as;
+      L.sc[0] = ds;
+      L.sc[1] = as;
     }
     __syncthreads();
-    if (L.nimg > 0) { dscale = L.fl2[0]; ascale = L.fl2[1]; }
+    if (L.nimg > 0) { dscale = L.sc[0]; ascale = L.sc[1]; }
     __syncthreads();
     if (L.nimg < s.minImageNum) {
       status = PMVS_FAIL_PRE;
@@ -836,7 +832,6 @@ __device__ void post_candidate(const DScene& s, WaveLds<WS>& L, const RefineJob&
       if (L.nimg < s.minImageNum) pfail = 1;
     }
     if (!pfail) {
-      set_grids<WS>(s, L, coord);
       int t = 0;
       for (int i = 0; i < L.nimg; ++i) t += (L.images[i] < s.tnum);
       timages = t;
@@ -848,8 +843,15 @@ __device__ void post_candidate(const DScene& s, WaveLds<WS>& L, const RefineJob&
   const int nout = L.nimg;
   for (int k = lane; k < PMVS_MAX_IMAGES; k += WAVE) {  // the unused tail is zero: the record's bytes are defined
     cout.images[k] = (k < nout) ? L.images[k] : 0;
-    cout.grids[k][0] = (k < nout && status == PMVS_ACCEPTED) ? L.grids[k][0] : 0;
-    cout.grids[k][1] = (k < nout && status == PMVS_ACCEPTED) ? L.grids[k][1] : 0;
+    int g0 = 0, g1 = 0;
+    if (k < nout && status == PMVS_ACCEPTED) {  // CPatchOrganizerS::setGrids, patchOrganizerS.cpp:410-419
+      float ic[3];
+      project(s.views[L.images[k]], coord, s.level, ic);
+      g0 = ((int)floorf(ic[0] + 0.5f)) / s.csize;
+      g1 = ((int)floorf(ic[1] + 0.5f)) / s.csize;
+    }
+    cout.grids[k][0] = g0;
+    cout.grids[k][1] = g1;
   }
   if (lane == 0) {
     cout.status = status;
@@ -1509,15 +1511,22 @@ namespace pmvsdev {
 // post are latency-bound wave-per-candidate walks: a 256-register budget (2 waves per SIMD, the
 // persistent grid's 8 per CU) instead of the 324 the inlined code would take (1 per SIMD).
 // Round 5: with the texture loops' unroll bounded (grab_batch, tex_dot) they fit 188 / 150
-// registers without spills, and 3 waves per SIMD measured best (r05w: pre 161 -> 144, post 207 ->
-// 200 ms per C3 step against round 4's 2 waves with spills; 4 waves no better).  PMVS_PREPOST_WPE:
-// the waves-per-SIMD target (timing variants).
+// registers without spills (r05w: pre 161 -> 144, post 207 -> 200 ms per C3 step against round 4's
+// spills).  Its 3-waves-per-SIMD target was not reached at WS = 7 then: WaveLds<7> took 19.3 KB, 8
+// workgroups per CU.  At 12.2 KB (the static_assert beside WaveLds) 12 fit, and pre / post /
+// filter_refimage run 3 waves per SIMD at WS <= 7: 144 / 177 / 151 -> 118 / 147 / 116 ms per C3 step
+// (profiles/r09a_prepost_3waves.json).  pre then holds 168 registers and spills 30; at 2 waves
+// (-DPMVS_PRE_WPE=2: 188 registers, none spilled) the step was no faster (+9 ms, inside the noise).
+// PMVS_PREPOST_WPE, PMVS_PRE_WPE: the waves-per-SIMD targets (timing variants).
 #ifndef PMVS_PREPOST_WPE
 #define PMVS_PREPOST_WPE 3
 #endif
-int prepost_waves() { return PMVS_PREPOST_WPE; }
+#ifndef PMVS_PRE_WPE
+#define PMVS_PRE_WPE PMVS_PREPOST_WPE
+#endif
+int prepost_waves() { return PMVS_PREPOST_WPE > PMVS_PRE_WPE ? PMVS_PREPOST_WPE : PMVS_PRE_WPE; }
 template <int WS>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PMVS_PREPOST_WPE))) void pre_kernel(DScene s, const pmvs_candidate* __restrict__ in,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PMVS_PRE_WPE))) void pre_kernel(DScene s, const pmvs_candidate* __restrict__ in,
                                                   RefineJob* __restrict__ jobs, float4* __restrict__ enc, int n,
                                                   DevStats* st) {
   __shared__ WaveLds<WS> L;
@@ -1621,16 +1630,16 @@ __global__ __launch_bounds__(64) void grab_tex_kernel(DScene s, const pmvs_tex_q
         for (int c = 0; c < xx; ++c) { lx = lx + L.jdx[0][0]; ly = ly + L.jdx[0][1]; }
         float rgb[3];
         get_color(s, s.views[L.jview[0]], lx, ly, L.jlevel[0], rgb);
-        L.tex[0][t][0] = rgb[0];
-        L.tex[0][t][1] = rgb[1];
-        L.tex[0][t][2] = rgb[2];
+        L.tex[0][3 * t + 0] = rgb[0];
+        L.tex[0][3 * t + 1] = rgb[1];
+        L.tex[0][3 * t + 2] = rgb[2];
       }
     }
     __syncthreads();
   }
   const int ok = L.valid[0];
   for (int t = lane; t < S; t += WAVE) {
-    for (int c = 0; c < 3; ++c) out[(size_t)i * 3 * S + 3 * t + c] = ok ? L.tex[0][t][c] : 0.0f;
+    for (int c = 0; c < 3; ++c) out[(size_t)i * 3 * S + 3 * t + c] = ok ? L.tex[0][3 * t + c] : 0.0f;
   }
   if (lane == 0) valid[i] = ok;
 }
@@ -1814,10 +1823,11 @@ static hipError_t launch_refine_ws(const DScene& s, const pmvs_candidate* d_in, 
   // pre / post: the persistent grid (2 single-wave workgroups per SIMD) scaled to their residency
   const int gp = grid * PMVS_PREPOST_WPE / 2;
   const int g = gp < n ? gp : n;
+  const int gpre = grid * PMVS_PRE_WPE / 2 < n ? grid * PMVS_PRE_WPE / 2 : n;
   hipError_t e = rh.ensure((size_t)n);
   if (e != hipSuccess) return e;
   (void)hipEventRecord(ev[0], stream);
-  hipLaunchKernelGGL((pre_kernel<WS>), dim3(g), dim3(64), 0, stream, s, d_in, d_jobs, rh.d_enc, n, d_st);
+  hipLaunchKernelGGL((pre_kernel<WS>), dim3(gpre), dim3(64), 0, stream, s, d_in, d_jobs, rh.d_enc, n, d_st);
   if (rh.prof && (rh.ev_pre || hipEventCreate(&rh.ev_pre) == hipSuccess)) (void)hipEventRecord(rh.ev_pre, stream);
   // the start point's angles with the host's libm (encode_angles_host): one round trip per batch
   if ((e = hipMemcpyAsync(rh.h_enc, rh.d_enc, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, stream)) != hipSuccess ||
@@ -2002,7 +2012,7 @@ __device__ __forceinline__ void apply_ref_list(const DScene& s, pmvs_patch& q, c
 // their outcome written to refpos[k] -- the list position swapped with position 0 (0: unchanged) or
 // -1 (no target image: list cleared); apply_refpos_kernel applies the all-gathered outcomes.
 template <int WS>
-__global__ __launch_bounds__(64) void filter_refimage_kernel(DScene s, pmvs_patch* __restrict__ P,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PMVS_PREPOST_WPE))) void filter_refimage_kernel(DScene s, pmvs_patch* __restrict__ P,
                                                              const int* __restrict__ list, int m, int* __restrict__ refpos,
                                                              int rank, int world) {
   __shared__ WaveLds<WS> L;
@@ -2063,7 +2073,8 @@ __global__ void apply_refpos_kernel(DScene s, pmvs_patch* __restrict__ P, const 
 hipError_t launch_filter_refimage(const DScene& s, pmvs_patch* P, const int* list, int m, int grid, hipStream_t stream,
                                   int* refpos, int rank, int world) {
   if (m <= 0) return hipSuccess;
-  const int g = grid < m ? grid : m;
+  const int gp = grid * PMVS_PREPOST_WPE / 2;  // pre / post's grid (launch_refine_ws); s.scratch has a slot for each
+  const int g = gp < m ? gp : m;
   switch (s.wsize) {
     case 5: hipLaunchKernelGGL((filter_refimage_kernel<5>), dim3(g), dim3(64), 0, stream, s, P, list, m, refpos, rank, world); break;
     case 7: hipLaunchKernelGGL((filter_refimage_kernel<7>), dim3(g), dim3(64), 0, stream, s, P, list, m, refpos, rank, world); break;
