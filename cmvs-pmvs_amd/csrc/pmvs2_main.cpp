@@ -31,6 +31,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
 #include <string>
 #include <thread>
@@ -361,37 +362,59 @@ int main(int argc, char* argv[]) {
   // (lowest target image holding the patch, its cell there), ties in model order.  The order, the
   // writers' fields and lists (index2image applied) and writePLY's colours are produced on the
   // device (pmvs_loop_export): only these arrays cross PCIe, not the model's records.
-  pmvs_export_sizes xs{};
-  CHECK("export", pmvs_loop_export_sizes(sc, &xs));
-  std::vector<float> fields((size_t)std::max(nmodel, 1) * 11);
-  std::vector<int32_t> colors((size_t)std::max(nmodel, 1) * 3);
-  std::vector<int64_t> ioff, voff;  // the lists only for the .patch file
-  std::vector<int32_t> ids, vids;
-  pmvs_export_buffers xb{};
-  xb.fields = fields.data();
-  xb.colors = colors.data();
-  if (export_patch) {
-    ioff.resize((size_t)nmodel + 1);
-    voff.resize((size_t)nmodel + 1);
-    ids.resize((size_t)std::max<int64_t>(xs.image_entries, 1));
-    vids.resize((size_t)std::max<int64_t>(xs.vimage_entries, 1));
-    xb.image_off = ioff.data();
-    xb.image_ids = ids.data();
-    xb.vimage_off = voff.data();
-    xb.vimage_ids = vids.data();
-  }
-  CHECK("export", pmvs_loop_export(sc, PMVS_EXPORT_WRITER_ORDER, images.data(), &xb));
-  std::vector<int32_t> nimg(nmodel), nvimg(nmodel);
-  for (int r = 0; r < nmodel && export_patch; ++r) {
-    nimg[r] = (int32_t)(ioff[r + 1] - ioff[r]);
-    nvimg[r] = (int32_t)(voff[r + 1] - voff[r]);
-  }
+  // The files' text is formatted on the device too (pmvs_loop_text): per file a size query, one buffer
+  // and one write.  PMVS_HOST_WRITERS=1 keeps the export arrays and the host writers (the same bytes).
   const std::string out = prefix + "models/" + option;
-  CHECK("ply", pmvs_write_ply((out + ".ply").c_str(), nmodel, fields.data(), colors.data()));
-  if (export_patch)
-    CHECK("patch", pmvs_write_patches((out + ".patch").c_str(), nmodel, fields.data(), nimg.data(), ids.data(),
-                                      nvimg.data(), vids.data()));
-  if (export_pset) CHECK("pset", pmvs_write_pset((out + ".pset").c_str(), nmodel, fields.data()));
+  if (env_int("PMVS_HOST_WRITERS", 0) == 0) {
+    const struct { int32_t kind; bool wanted; const char* ext; } files[] = {
+        {PMVS_TEXT_PLY, true, ".ply"}, {PMVS_TEXT_PATCH, export_patch, ".patch"}, {PMVS_TEXT_PSET, export_pset, ".pset"}};
+    std::vector<char> text;
+    for (const auto& f : files) {
+      if (!f.wanted) continue;
+      int64_t size = 0;
+      CHECK(f.ext, pmvs_loop_text(sc, f.kind, PMVS_EXPORT_WRITER_ORDER, images.data(), nullptr, 0, &size));
+      if ((int64_t)text.size() < size) text.resize((size_t)size);
+      CHECK(f.ext, pmvs_loop_text(sc, f.kind, PMVS_EXPORT_WRITER_ORDER, images.data(), text.data(), size, &size));
+      std::ofstream os(out + f.ext, std::ios::binary);
+      os.write(text.data(), (std::streamsize)size);
+      os.close();
+      if (!os) {
+        std::cerr << "pmvs2: cannot write " << out << f.ext << std::endl;
+        return 1;
+      }
+    }
+  } else {
+    pmvs_export_sizes xs{};
+    CHECK("export", pmvs_loop_export_sizes(sc, &xs));
+    std::vector<float> fields((size_t)std::max(nmodel, 1) * 11);
+    std::vector<int32_t> colors((size_t)std::max(nmodel, 1) * 3);
+    std::vector<int64_t> ioff, voff;  // the lists only for the .patch file
+    std::vector<int32_t> ids, vids;
+    pmvs_export_buffers xb{};
+    xb.fields = fields.data();
+    xb.colors = colors.data();
+    if (export_patch) {
+      ioff.resize((size_t)nmodel + 1);
+      voff.resize((size_t)nmodel + 1);
+      ids.resize((size_t)std::max<int64_t>(xs.image_entries, 1));
+      vids.resize((size_t)std::max<int64_t>(xs.vimage_entries, 1));
+      xb.image_off = ioff.data();
+      xb.image_ids = ids.data();
+      xb.vimage_off = voff.data();
+      xb.vimage_ids = vids.data();
+    }
+    CHECK("export", pmvs_loop_export(sc, PMVS_EXPORT_WRITER_ORDER, images.data(), &xb));
+    std::vector<int32_t> nimg(nmodel), nvimg(nmodel);
+    for (int r = 0; r < nmodel && export_patch; ++r) {
+      nimg[r] = (int32_t)(ioff[r + 1] - ioff[r]);
+      nvimg[r] = (int32_t)(voff[r + 1] - voff[r]);
+    }
+    CHECK("ply", pmvs_write_ply((out + ".ply").c_str(), nmodel, fields.data(), colors.data()));
+    if (export_patch)
+      CHECK("patch", pmvs_write_patches((out + ".patch").c_str(), nmodel, fields.data(), nimg.data(), ids.data(),
+                                        nvimg.data(), vids.data()));
+    if (export_pset) CHECK("pset", pmvs_write_pset((out + ".pset").c_str(), nmodel, fields.data()));
+  }
   if (export_depth) {
     // what each target image sees of the model just written (CFilter::setDepthMaps over it, on the
     // device): the depth of the nearest patch per cell, one PFM per target image

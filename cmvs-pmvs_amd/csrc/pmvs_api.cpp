@@ -21,6 +21,7 @@
 
 #include "../../include/pmvs_amd.h"
 #include "pmvs_features.h"
+#include "pmvs_fmt.h"
 #include "pmvs_launch.h"
 
 using namespace pmvsdev;
@@ -1675,6 +1676,132 @@ pmvs_status pmvs_depth_maps_patches(pmvs_scene* sc, const pmvs_patch* patches, i
     EXPCHK(hipMemcpyAsync(dP, patches, (size_t)n * sizeof(pmvs_patch), hipMemcpyHostToDevice, sc->stream));
   }
   return depth_maps_records(sc, dP, n, flags, buffers);
+}
+
+// ---- text files (pmvs_text.hip)
+namespace {
+bool text_args_ok(const pmvs_scene* sc, int32_t kind, int32_t flags, const char* out, int64_t cap, const int64_t* bytes) {
+  return sc && bytes && (kind == PMVS_TEXT_PLY || kind == PMVS_TEXT_PATCH || kind == PMVS_TEXT_PSET) &&
+         !(flags & ~(PMVS_EXPORT_WRITER_ORDER | PMVS_EXPORT_DEVICE)) && cap >= 0 && (out || cap == 0);
+}
+
+// The header of a `kind` file of n patches (pmvs_io.cpp's writers).
+std::string text_header(int32_t kind, int32_t n) {
+  if (kind == PMVS_TEXT_PLY)
+    return "ply\nformat ascii 1.0\nelement vertex " + std::to_string(n) +
+           "\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\n"
+           "property float nz\nproperty uchar diffuse_red\nproperty uchar diffuse_green\n"
+           "property uchar diffuse_blue\nproperty float quality\nend_header\n";
+  if (kind == PMVS_TEXT_PATCH) return "PATCHES\n" + std::to_string(n) + "\n";
+  return std::string();
+}
+
+// The text of the device records dP[0, n); sz = their totals.
+pmvs_status text_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, const pmvs_export_sizes& sz, int32_t kind,
+                         int32_t flags, const int32_t* index2image, char* out, int64_t cap, int64_t* bytes) {
+  const bool dev = (flags & PMVS_EXPORT_DEVICE) != 0;
+  const std::string header = text_header(kind, n);
+  ExportTemp tmp;
+  TextArrays t;
+  long long* d_off = nullptr;
+  int64_t total = (int64_t)header.size();
+  if (n > 0) {
+    // the export's arrays this kind reads, into call-scoped scratch
+    const size_t np = (size_t)n;
+    ExportArrays a;
+    EXPCHK(tmp.alloc(&a.fields, np * 11));
+    if (kind == PMVS_TEXT_PLY) EXPCHK(tmp.alloc(&a.colors, np * 3));
+    if (kind == PMVS_TEXT_PATCH) {
+      EXPCHK(tmp.alloc(&a.image_off, np + 1));
+      EXPCHK(tmp.alloc(&a.image_ids, (size_t)sz.image_entries));
+      EXPCHK(tmp.alloc(&a.vimage_off, np + 1));
+      EXPCHK(tmp.alloc(&a.vimage_ids, (size_t)sz.vimage_entries));
+    }
+    int* d_tab = nullptr;
+    if (index2image && kind == PMVS_TEXT_PATCH) {
+      EXPCHK(tmp.alloc(&d_tab, (size_t)sc->ds.num));
+      EXPCHK(hipMemcpyAsync(d_tab, index2image, (size_t)sc->ds.num * sizeof(int), hipMemcpyHostToDevice, sc->stream));
+    }
+    const int max_gwidth = depth_map_layout(sc, nullptr, nullptr);
+    EXPCHK(export_pass(sc->ds, dP, n, (flags & PMVS_EXPORT_WRITER_ORDER) != 0, max_gwidth, d_tab, a, sc->stream));
+    t.fields = a.fields; t.colors = a.colors; t.image_off = a.image_off; t.image_ids = a.image_ids;
+    t.vimage_off = a.vimage_off; t.vimage_ids = a.vimage_ids;
+    EXPCHK(tmp.alloc(&d_off, np + 1));
+    EXPCHK(text_offsets(kind, t, n, (long long)header.size(), d_off, sc->stream));
+    long long end = 0;
+    EXPCHK(hipMemcpyAsync(&end, d_off + n, sizeof(end), hipMemcpyDeviceToHost, sc->stream));
+    EXPCHK(hipStreamSynchronize(sc->stream));
+    total = end;
+  }
+  *bytes = total;
+  if (!out && cap == 0) return PMVS_OK;  // the size query
+  if (cap < total) return fail(PMVS_EINVAL, "text: the buffer holds %lld bytes, the text has %lld", (long long)cap, (long long)total);
+  if (total == 0) return PMVS_OK;
+  char* d_out = out;
+  if (!dev) {
+    if (n == 0) {
+      std::memcpy(out, header.data(), header.size());
+      return PMVS_OK;
+    }
+    EXPCHK(tmp.alloc(&d_out, (size_t)total));
+  }
+  if (!header.empty()) EXPCHK(hipMemcpyAsync(d_out, header.data(), header.size(), hipMemcpyHostToDevice, sc->stream));
+  EXPCHK(text_write(kind, t, n, d_off, d_out, sc->stream));
+  if (!dev) EXPCHK(hipMemcpyAsync(out, d_out, (size_t)total, hipMemcpyDeviceToHost, sc->stream));
+  // the scratch and the header are freed on return: the work that reads them must have finished
+  EXPCHK(hipStreamSynchronize(sc->stream));
+  return PMVS_OK;
+}
+}  // namespace
+
+pmvs_status pmvs_loop_text(pmvs_scene* sc, int32_t kind, int32_t flags, const int32_t* index2image, char* out,
+                           int64_t cap, int64_t* bytes) {
+  if (!text_args_ok(sc, kind, flags, out, cap, bytes)) return fail(PMVS_EINVAL, "invalid argument");
+  if (sc->lkept < 0) return fail(PMVS_EINVAL, "loop_text: no loop result on the device");
+  HIPCHK(hipSetDevice(sc->device));
+  pmvs_export_sizes sz{};
+  if (pmvs_status st = device_export_sizes(sc, sc->fpatches.p, sc->lkept, &sz)) return st;
+  return text_records(sc, sc->fpatches.p, sc->lkept, sz, kind, flags, index2image, out, cap, bytes);
+}
+
+pmvs_status pmvs_text_patches(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, int32_t kind, int32_t flags,
+                              const int32_t* index2image, char* out, int64_t cap, int64_t* bytes) {
+  if (!text_args_ok(sc, kind, flags, out, cap, bytes) || n < 0 || (n > 0 && !patches))
+    return fail(PMVS_EINVAL, "invalid argument");
+  pmvs_export_sizes sz{};
+  if (pmvs_status st = check_export_patches(sc, patches, n, &sz)) return st;
+  HIPCHK(hipSetDevice(sc->device));
+  // a buffer of its own: sc->fpatches may hold a loop result
+  ExportTemp tmp;
+  pmvs_patch* dP = nullptr;
+  if (n) {
+    EXPCHK(tmp.alloc(&dP, (size_t)n));
+    EXPCHK(hipMemcpyAsync(dP, patches, (size_t)n * sizeof(pmvs_patch), hipMemcpyHostToDevice, sc->stream));
+  }
+  return text_records(sc, dP, n, sz, kind, flags, index2image, out, cap, bytes);
+}
+
+pmvs_status pmvs_selftest_format(int32_t device, int32_t precision, const float* in, int32_t n, char* out, int32_t* len) {
+  if (!in || !out || !len || n <= 0 || (precision != 6 && precision != 17)) return fail(PMVS_EINVAL, "invalid argument");
+  if (device == -1) {  // the same source on the host
+    std::memset(out, 0, (size_t)n * 24);
+    for (int i = 0; i < n; ++i) len[i] = pmvsfmt::fmt_g(in[i], precision, out + (size_t)i * 24);
+    return PMVS_OK;
+  }
+  HIPCHK(hipSetDevice(device));
+  ExportTemp tmp;
+  float* d_in = nullptr;
+  char* d_out = nullptr;
+  int* d_len = nullptr;
+  EXPCHK(tmp.alloc(&d_in, (size_t)n));
+  EXPCHK(tmp.alloc(&d_out, (size_t)n * 24));
+  EXPCHK(tmp.alloc(&d_len, (size_t)n));
+  EXPCHK(hipMemcpy(d_in, in, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  EXPCHK(hipMemset(d_out, 0, (size_t)n * 24));
+  EXPCHK(launch_format_selftest(precision, d_in, n, d_out, d_len, nullptr));
+  EXPCHK(hipMemcpy(out, d_out, (size_t)n * 24, hipMemcpyDeviceToHost));
+  EXPCHK(hipMemcpy(len, d_len, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  return PMVS_OK;
 }
 
 pmvs_status pmvs_scene_set_shard(pmvs_scene* sc, int32_t rank, int32_t world, pmvs_allgather_fn fn, void* ctx) {

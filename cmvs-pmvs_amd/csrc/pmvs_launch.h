@@ -90,6 +90,22 @@ hipError_t export_pass(const DScene& s, const pmvs_patch* P, int n, bool writer_
 hipError_t export_order(const DScene& s, const pmvs_patch* P, int n, int max_gwidth, int* sorted, int* cnt_i, int* cnt_v,
                         hipStream_t st);
 
+// ---- text files (pmvs_text.hip)
+// The export's device arrays a text kind reads: fields always, colors for .ply, the lists for .patch.
+struct TextArrays {
+  const float* fields = nullptr;
+  const int* colors = nullptr;
+  const long long *image_off = nullptr, *vimage_off = nullptr;
+  const int *image_ids = nullptr, *vimage_ids = nullptr;
+};
+// The byte offset of every row of the PMVS_TEXT_* `kind` file in d_off (n + 1 device entries: the first
+// is header_bytes, the last the file's size).  Returns after the stream has finished the work.
+hipError_t text_offsets(int kind, const TextArrays& in, int n, long long header_bytes, long long* d_off, hipStream_t st);
+// Formats the n rows at their offsets in d_out (queued on the stream).
+hipError_t text_write(int kind, const TextArrays& in, int n, const long long* d_off, char* d_out, hipStream_t st);
+// pmvsfmt::fmt_g of n floats as a kernel: d_out n x 24 bytes, d_len n.
+hipError_t launch_format_selftest(int precision, const float* d_in, int n, char* d_out, int* d_len, hipStream_t st);
+
 // ---- per-target depth maps (pmvs_depthmap.hip)
 // Device pointers of the arrays of pmvs_depthmap_buffers (include/pmvs_amd.h); null = not wanted.
 struct DepthMapArrays {

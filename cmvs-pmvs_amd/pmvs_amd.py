@@ -113,6 +113,7 @@ class ExportBuffers(C.Structure):  # pmvs_export_buffers
 
 
 EXPORT_WRITER_ORDER, EXPORT_DEVICE = 1, 2
+TEXT_PLY, TEXT_PATCH, TEXT_PSET = 0, 1, 2  # PMVS_TEXT_*: the kinds of pmvs_loop_text / pmvs_text_patches
 
 
 class DepthMapBuffers(C.Structure):  # pmvs_depthmap_buffers
@@ -163,6 +164,7 @@ EXPORTS = ["pmvs_last_error", "pmvs_device_count", "pmvs_scene_create", "pmvs_sc
            "pmvs_expand_run", "pmvs_expand_fetch", "pmvs_run_loop", "pmvs_loop_fetch", "pmvs_loop_hash",
            "pmvs_loop_export_sizes", "pmvs_loop_export", "pmvs_export_patches_sizes", "pmvs_export_patches",
            "pmvs_depth_map_layout", "pmvs_loop_depth_maps", "pmvs_depth_maps_patches", "pmvs_write_pfm",
+           "pmvs_loop_text", "pmvs_text_patches", "pmvs_selftest_format",
            "pmvs_scene_set_shard", "pmvs_scene_set_shard_rccl", "pmvs_scene_set_cluster",
            "pmvs_scene_set_cluster_rccl", "pmvs_rccl_unique_id",
            "pmvs_rccl_create", "pmvs_rccl_destroy", "pmvs_rccl_allgather", "pmvs_rccl_allgather_device",
@@ -238,6 +240,11 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.pmvs_loop_depth_maps.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DepthMapBuffers)]
     lib.pmvs_depth_maps_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DepthMapBuffers)]
     lib.pmvs_write_pfm.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.pmvs_loop_text.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                   C.POINTER(C.c_int64)]
+    lib.pmvs_text_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                      C.c_int64, C.POINTER(C.c_int64)]
+    lib.pmvs_selftest_format.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.pmvs_scene_set_shard.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.pmvs_scene_set_cluster.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pmvs_scene_set_cluster_rccl.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
@@ -671,6 +678,47 @@ class Scene:
         _check(self.lib.pmvs_depth_maps_patches(self.handle, _ptr(pa), len(pa), flags, C.byref(buf)))
         return out
 
+    def _text(self, call, device: bool, out):
+        """A size query, the buffer (numpy uint8, or a torch uint8 tensor on the scene's device; `out`
+        supplies it) and the call that fills it; returns the buffer cut to the text's size."""
+        size = C.c_int64(0)
+        _check(call(None, 0, C.byref(size)))
+        n = int(size.value)
+        if device:
+            import torch
+            if out is None:
+                out = torch.empty(n, dtype=torch.uint8, device=torch.device("cuda", self.device))
+            cap, ptr = out.numel(), (out.data_ptr() if out.numel() else None)
+        else:
+            if out is None:
+                out = np.empty(n, np.uint8)
+            cap, ptr = out.size, (out.ctypes.data if out.size else None)
+        if n > cap:
+            raise PmvsError(f"the text has {n} bytes, `out` holds {cap}")
+        if n:
+            _check(call(ptr, cap, C.byref(size)))
+        return out[:n]
+
+    def loop_text(self, kind: int, writer_order: bool = True, index2image=None, device: bool = False, out=None):
+        """pmvs_loop_text: the .ply / .patch / .pset text (kind = TEXT_PLY / TEXT_PATCH / TEXT_PSET) of
+        the last run_loop(fetch=False) result, formatted on the device: the bytes write_ply /
+        write_patches / write_pset write from loop_export of the same flags, as a numpy uint8 array
+        (device=True: a torch uint8 tensor on the scene's device, nothing crosses PCIe).  Does not
+        consume the result.  out: a uint8 buffer of at least the text's size to use."""
+        tab = self._index2image(index2image)
+        flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
+        return self._text(lambda ptr, cap, size: self.lib.pmvs_loop_text(self.handle, kind, flags, _ptr(tab), ptr, cap, size),
+                          device, out)
+
+    def text_patches(self, patches: np.ndarray, kind: int, writer_order: bool = True, index2image=None,
+                     device: bool = False, out=None):
+        """pmvs_text_patches: loop_text's bytes for caller-supplied PATCH_DTYPE records."""
+        pa = np.ascontiguousarray(patches, PATCH_DTYPE)
+        tab = self._index2image(index2image)
+        flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
+        return self._text(lambda ptr, cap, size: self.lib.pmvs_text_patches(self.handle, _ptr(pa), len(pa), kind, flags,
+                                                                            _ptr(tab), ptr, cap, size), device, out)
+
     def patch_colors(self, coords: np.ndarray, images) -> np.ndarray:
         """writePLY colour mode 0 for patches (coords [n,4], images: list of view-index lists)."""
         coords = np.ascontiguousarray(coords, np.float32).reshape(-1, 4)
@@ -707,6 +755,18 @@ def selftest_math(op: int, x: np.ndarray, device: int = 0) -> np.ndarray:
     out = np.zeros_like(x)
     _check(load_library().pmvs_selftest_math(device, op, _ptr(x), _ptr(out), len(x)))
     return out
+
+
+def selftest_format(precision: int, x: np.ndarray, device: int = 0):
+    """pmvs_selftest_format: the text kernels' number formatter (csrc/pmvs_fmt.h) on float32 values, as a
+    list of bytes -- what printf("%.{precision}g") prints; device=-1 runs the same source on the host."""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    out = np.zeros((len(x), 24), np.uint8)
+    ln = np.zeros(len(x), np.int32)
+    if len(x):
+        _check(load_library().pmvs_selftest_format(device, precision, _ptr(x), len(x), _ptr(out), _ptr(ln)))
+    raw = out.tobytes()
+    return [raw[24 * i:24 * i + int(k)] for i, k in enumerate(ln)]
 
 
 def selftest_lls(systems, device: int = 0) -> np.ndarray:

@@ -411,6 +411,37 @@ pmvs_status pmvs_loop_depth_maps(pmvs_scene* scene, int32_t flags, const pmvs_de
 pmvs_status pmvs_depth_maps_patches(pmvs_scene* scene, const pmvs_patch* patches, int32_t n, int32_t flags,
                                     const pmvs_depthmap_buffers* buffers);
 
+/* The .ply / .patch / .pset text of the model, formatted on the device: the bytes pmvs_write_ply /
+ * pmvs_write_patches / pmvs_write_pset write from the export of the same records and flags
+ * (CPatchOrganizerS::writePLY patchOrganizerS.cpp:687-776, writePatches2 :89-132 with Patch::operator<<
+ * patch.cpp:31-48; `ostream << float` at precision 17, the .pset at 6), as one contiguous buffer that the
+ * caller writes with one call.  The rows, index2image and the colours come from the export's code; every
+ * row is formatted independently, a 64-bit scan of the rows' byte counts places them.
+ * flags: PMVS_EXPORT_WRITER_ORDER and PMVS_EXPORT_DEVICE (then `out` is a device pointer on the scene's
+ * device) and no other bit.  *bytes receives the text's size; out == NULL with cap == 0 is the size query
+ * and writes nothing else.  PMVS_EINVAL: cap smaller than the size (*bytes is set), a kind that is not
+ * PMVS_TEXT_*, another flag bit, a NULL scene or a NULL bytes.  Zero patches give the header alone (the
+ * .pset has none).  Scratch (the export's arrays, 16 bytes per row and, in host mode, the text) is
+ * allocated for the call and freed on return; the work is queued on the scene's stream and the call
+ * returns after it has finished. */
+#define PMVS_TEXT_PLY 0
+#define PMVS_TEXT_PATCH 1
+#define PMVS_TEXT_PSET 2
+/* Reads the result pmvs_run_loop left on the device (PMVS_EINVAL when there is none) and does not consume
+ * it: pmvs_loop_hash, pmvs_loop_fetch, pmvs_loop_export and pmvs_loop_depth_maps still work afterwards. */
+pmvs_status pmvs_loop_text(pmvs_scene* scene, int32_t kind, int32_t flags, const int32_t* index2image,
+                           char* out, int64_t cap, int64_t* bytes);
+/* The same for caller-supplied records: uploaded once and validated as pmvs_export_patches validates
+ * them (PMVS_EINVAL). */
+pmvs_status pmvs_text_patches(pmvs_scene* scene, const pmvs_patch* patches, int32_t n, int32_t kind, int32_t flags,
+                              const int32_t* index2image, char* out, int64_t cap, int64_t* bytes);
+/* Self-test of the number formatter the text kernels use (csrc/pmvs_fmt.h): the bytes of
+ * printf("%.{precision}g", (double)in[i]) in out + 24 * i (zero-filled behind them) and their number in
+ * len[i].  device == -1 runs it on the host, otherwise as a kernel on that device.  precision is 6 or 17
+ * (PMVS_EINVAL otherwise). */
+pmvs_status pmvs_selftest_format(int32_t device, int32_t precision, const float* in, int32_t n,
+                                 char* out /* n x 24 */, int32_t* len /* n */);
+
 /* The seed phase, PMVS3::CSeed::init + run (seed.cpp:11-107) at CPU 1: target images in the
  * reference's std::shuffle(mt19937(42)) order, cells in raster order, the feature points of every
  * view (points: num_points[0] of view 0, then view 1, ..., as pmvs_detect_features returns them)
