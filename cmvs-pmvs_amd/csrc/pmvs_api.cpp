@@ -150,37 +150,6 @@ void build_binary(std::vector<uint8_t>* pyr, const int* w, const int* h, int max
   }
 }
 
-// PMVS_POISON_ALLOC=<byte>: fill new device allocations with that byte (uninitialised-read hunting).
-inline void poison_alloc(void* p, size_t bytes) {
-  static const int v = [] {
-    const char* e = getenv("PMVS_POISON_ALLOC");
-    return e ? atoi(e) : -1;
-  }();
-  if (v >= 0 && p && bytes) {
-    (void)hipMemset(p, v & 0xff, bytes);
-    (void)hipDeviceSynchronize();
-  }
-}
-
-template <class T>
-struct DBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  hipError_t alloc(size_t count) {
-    release();
-    n = count;
-    if (count == 0) return hipSuccess;
-    const hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
-    if (e == hipSuccess) poison_alloc(p, count * sizeof(T));
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-};
-
 }  // namespace
 
 struct pmvs_scene {
@@ -192,18 +161,18 @@ struct pmvs_scene {
   DScene ds{};
   int maxLevel = 0;
   std::vector<DView> hviews;
-  DBuf<DView> views;
-  DBuf<uint32_t> pyr;
-  DBuf<uint8_t> masks, edges;
-  DBuf<int> vis_off, vis, bindexes;
-  DBuf<float> scratch;
-  DBuf<DevStats> stats;
-  DBuf<RefineJob> jobs;
+  DevBuf<DView> views;
+  DevBuf<uint32_t> pyr;
+  DevBuf<uint8_t> masks, edges;
+  DevBuf<int> vis_off, vis, bindexes;
+  DevBuf<float> scratch;
+  DevBuf<DevStats> stats;
+  DevBuf<RefineJob> jobs;
   FilterBuffers fbuf;
   ExpandBuffers xbuf;
-  DBuf<pmvs_patch> fpatches;
-  DBuf<int> fkeep;
-  DBuf<unsigned long long> digest;  // pmvs_loop_hash
+  DevBuf<pmvs_patch> fpatches;
+  DevBuf<int> fkeep;
+  DevBuf<unsigned long long> digest;  // pmvs_loop_hash
   int grid = 0, refine_grid = 0, tslots = 226014;
   // batches below small_n candidates run the lane form, one candidate per wavefront with its BOBYQA
   // state over the lanes (tslots_small, pmvs_refine_lane.hip): their length is one chain's latency,
@@ -221,8 +190,8 @@ struct pmvs_scene {
   pmvs_allgather_fn cl_fn = nullptr;
   void* cl_ctx = nullptr;
   pmvs_rccl* cl_rccl = nullptr;
-  DBuf<unsigned char> cl_shared;
-  DBuf<int> cl_ids, cl_id2idx;
+  DevBuf<unsigned char> cl_shared;
+  DevBuf<int> cl_ids, cl_id2idx;
   int cl_maxid = -1;
   ClusterBuffers cbuf;
   RefineHost rhost;             // host libm step of every refine batch (launch_refine)
@@ -230,25 +199,21 @@ struct pmvs_scene {
   std::vector<pmvs_patch> skept; // seeds kept for pmvs_seed_fetch (pmvs_seed_run with out = NULL, cap = 0)
   bool seeds_kept = false;
   std::vector<int> xalive;
-  DBuf<pmvs_patch> fpatches2;   // compaction target of pmvs_run_loop
+  DevBuf<pmvs_patch> fpatches2;   // compaction target of pmvs_run_loop
   FeatBuffers feat;             // feature-detection scratch (pmvs_detect_features)
   // host copies the seed phase's control logic reads (canAdd masks, collectImages inputs)
   std::vector<std::vector<uint8_t>> hmask_level;  // per view, the binary mask at the scene level (empty = none)
   std::vector<int> hvis_off, hvis;
   int sequence = -1;
   // staging for host-pointer calls
-  DBuf<pmvs_candidate> cand;
-  DBuf<pmvs_refined> res;
-  DBuf<pmvs_eval_query> evq;
-  DBuf<double> evout;
-  DBuf<pmvs_tex_query> tq;
-  DBuf<float> tout;
-  DBuf<int> tvalid;
+  DevBuf<pmvs_candidate> cand;
+  DevBuf<pmvs_refined> res;
+  DevBuf<pmvs_eval_query> evq;
+  DevBuf<double> evout;
+  DevBuf<pmvs_tex_query> tq;
+  DevBuf<float> tout;
+  DevBuf<int> tvalid;
   ~pmvs_scene() {
-    cl_shared.release(); cl_ids.release(); cl_id2idx.release();
-    fpatches2.release(); views.release(); pyr.release(); masks.release(); edges.release(); vis_off.release(); vis.release();
-    bindexes.release(); scratch.release(); stats.release(); jobs.release(); fpatches.release(); fkeep.release(); digest.release(); cand.release(); res.release(); evq.release();
-    evout.release(); tq.release(); tout.release(); tvalid.release();
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
     for (hipEvent_t e : kev)
@@ -260,21 +225,14 @@ struct pmvs_scene {
 
 namespace {
 template <class T>
-pmvs_status ensure(DBuf<T>& b, size_t n) {
-  if (b.n >= n) return PMVS_OK;
+pmvs_status ensure(DevBuf<T>& b, size_t n) {
+  if (b.cap >= n) return PMVS_OK;
   hipError_t e = b.alloc(n);
   if (e != hipSuccess) return fail(PMVS_ENOMEM, "hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(e));
   return PMVS_OK;
 }
 int grow_alive(pmvs_scene* sc, int n) {
-  ExpandBuffers& X = sc->xbuf;
-  if ((size_t)n <= X.cap_alive && X.alive) return 0;
-  if (X.alive) (void)hipFree(X.alive);
-  X.alive = nullptr;
-  X.cap_alive = (size_t)n;
-  if (hipMalloc((void**)&X.alive, (size_t)n * sizeof(int)) != hipSuccess) return 1;
-  poison_alloc(X.alive, (size_t)n * sizeof(int));
-  return 0;
+  return sc->xbuf.alive.grow((size_t)n) != hipSuccess;
 }
 }  // namespace
 
@@ -360,7 +318,7 @@ pmvs_status pmvs_scene_create(const pmvs_scene_desc* d, int32_t device, pmvs_sce
   }
   if (hipMalloc((void**)&sc->pyr.p, words * sizeof(uint32_t)) != hipSuccess)
     return bail(fail(PMVS_ENOMEM, "pyramid: %lld words", words));
-  sc->pyr.n = words;
+  sc->pyr.cap = words;
   if (memset_big(sc->pyr.p, 0, words * sizeof(uint32_t), sc->stream) != hipSuccess)
     return bail(fail(PMVS_EDEVICE, "pyramid: clearing %lld words", words));
 
@@ -434,7 +392,7 @@ pmvs_status pmvs_scene_create(const pmvs_scene_desc* d, int32_t device, pmvs_sce
   }
 
   // ---- optional masks / edges (binary pyramids built on the host)
-  auto upload_binary = [&](bool any, bool isMask, DBuf<uint8_t>& buf) -> pmvs_status {
+  auto upload_binary = [&](bool any, bool isMask, DevBuf<uint8_t>& buf) -> pmvs_status {
     if (!any) return PMVS_OK;
     std::vector<uint8_t> all;
     for (int i = 0; i < num; ++i) {
@@ -1151,7 +1109,7 @@ pmvs_status expand_device(pmvs_scene* sc, int n0, int wave, int min_cands, int c
   const Shard sh = make_shard(sc);
   long long sv[8];
   const auto t0 = std::chrono::steady_clock::now();
-  const hipError_t e = expand_pass(sc->ds, sc->fbuf, sc->xbuf, sc->fpatches.p, sc->fpatches.n, n0, sc->xbuf.alive, cap,
+  const hipError_t e = expand_pass(sc->ds, sc->fbuf, sc->xbuf, sc->fpatches.p, sc->fpatches.cap, n0, sc->xbuf.alive, cap,
                                    tgoff[sc->ds.tnum], tgoff.data(), wave, cthr, flags, sc->grid, sc->stream, refine, sh,
                                    sv, n_out, min_cands);
   if (handled) *handled = e != hipSuccess;  // expand_pass ends every failure with a header all ranks see
@@ -1323,7 +1281,7 @@ pmvs_status pmvs_run_loop(pmvs_scene* sc, const pmvs_patch* seeds, int32_t n, fl
   // released after the swap when it is much larger than the model.
   bool dst_oom = false;
   auto dst_for = [&](int k, pmvs_patch** d) -> hipError_t {
-    if (sc->fpatches2.n > 2 * (size_t)std::max(k, 1)) sc->fpatches2.release();
+    if (sc->fpatches2.cap > 2 * (size_t)std::max(k, 1)) sc->fpatches2.release();
     if (ensure(sc->fpatches2, std::max(k, 1))) {
       dst_oom = true;
       return hipErrorOutOfMemory;
@@ -1332,9 +1290,8 @@ pmvs_status pmvs_run_loop(pmvs_scene* sc, const pmvs_patch* seeds, int32_t n, fl
     return hipSuccess;
   };
   auto swap_models = [&](int kept) {
-    std::swap(sc->fpatches.p, sc->fpatches2.p);
-    std::swap(sc->fpatches.n, sc->fpatches2.n);
-    if (sc->fpatches2.n > 2 * (size_t)std::max(kept, 1)) sc->fpatches2.release();
+    std::swap(sc->fpatches, sc->fpatches2);
+    if (sc->fpatches2.cap > 2 * (size_t)std::max(kept, 1)) sc->fpatches2.release();
   };
   // the model without foreign patches, compacted through fpatches2
   auto drop = [&](int n, int* kept) -> pmvs_status {
@@ -1387,7 +1344,7 @@ pmvs_status pmvs_run_loop(pmvs_scene* sc, const pmvs_patch* seeds, int32_t n, fl
       long long xs[3] = {0, 0, 0};
       bool agreed = false;
       int nn2 = own;
-      const hipError_t xe = cluster_exchange(sc->ds, sc->cbuf, cm, sc->fpatches.p, own, sc->fpatches.p, sc->fpatches.n, &nn2,
+      const hipError_t xe = cluster_exchange(sc->ds, sc->cbuf, cm, sc->fpatches.p, own, sc->fpatches.p, sc->fpatches.cap, &nn2,
                                              csh, sc->stream, xs, agreed);
       if (xe != hipSuccess) return fail_loop(fail(PMVS_EDEVICE, "cluster exchange: %s", hipGetErrorString(xe)), agreed);
       cur = nn2;

@@ -1,4 +1,6 @@
-// pmvs_filter.hip -- one PMVS filter pass (PMVS3::CFilter::run, filter.cpp:13-27) on the device.
+// pmvs_filter.hip -- the device loop: the patch organizer, one PMVS filter pass (PMVS3::CFilter::run,
+// filter.cpp:13-27), one expansion run (CExpand::run) with its device commit, the loop helpers and the
+// CMVS cluster exchange, each under its own banner below.
 //
 // The reference keeps CPatchOrganizerS cell lists of shared_ptrs (pgrids / vpgrids / dpgrids,
 // patchOrganizerS.cpp) and walks them with CPU threads.  Here the organizer is rebuilt on the
@@ -22,19 +24,15 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
-#include <new>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
-#include <sys/mman.h>
-#include <deque>
 #include <functional>
 #include <mutex>
 #include <unordered_map>
-#include <queue>
 #include <vector>
 
 #include "pmvs_device.h"
@@ -43,19 +41,6 @@
 #include "pmvs_queue.h"
 
 namespace pmvsdev {
-
-// Debug builds of the tests: PMVS_POISON_ALLOC=<byte> fills every new device allocation with that
-// byte, so a read of memory no kernel wrote shows up as a result change (tests/test_gpu_poison.py).
-inline void poison_alloc(void* p, size_t bytes) {
-  static const int v = [] {
-    const char* e = getenv("PMVS_POISON_ALLOC");
-    return e ? atoi(e) : -1;
-  }();
-  if (v >= 0 && p && bytes) {
-    (void)hipMemset(p, v & 0xff, bytes);
-    (void)hipDeviceSynchronize();
-  }
-}
 
 // Neighbours per patch the walks hold in LDS.  The NB_CAP form runs every walk; the few patches
 // with more unique neighbours are walked again by the NB_CAP_BIG form (NbLdsT<16384>, about 130 KB
@@ -1635,7 +1620,6 @@ __global__ __launch_bounds__(64) NB_WALK_ATTR void neighbor_kernel(DScene s, Fil
 // the row pool is 64 x (first lane's n) rows; element (row i, column j; j = 5 is Q^T b) of lane l
 // sits at pool[6 * qoff[chunk] + (6 i + j) * 64 + l], so every column walk is a coalesced 512-B
 // access.  The 5 x 5 Jacobi stage runs in registers.
-__device__ __forceinline__ double dmaxd2(double a, double b) { return (a < b) ? b : a; }  // std::max
 __global__ void quad_chunk_rows_kernel(const unsigned long long* __restrict__ qsorted, int njobs, int* __restrict__ crows) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c * 64 < njobs) crows[c] = 64 * (2047 - (int)(qsorted[(size_t)c * 64] >> 32));
@@ -1678,7 +1662,7 @@ __device__ inline void quad_lane_job(const DScene& s, const FilterDev& F, const 
     const double a[5] = {(double)(fx * fx), (double)(fy * fy), (double)(fx * fy), (double)fx, (double)fy};
     for (int j = 0; j < N; ++j) {
       M[(size_t)(6 * i + j) * 64] = a[j];
-      scale = dmaxd2(scale, fabs(a[j]));
+      scale = dmaxd(scale, fabs(a[j]));
     }
     M[(size_t)(6 * i + 5) * 64] = (double)gz[i];
   }
@@ -1780,7 +1764,7 @@ __device__ inline void quad_solve(const DScene& s, const FilterDev& F, const dou
         U[i][j] = V[i][j] = (i == j) ? 1.0 : 0.0;
       }
     double maxd = 0.0;
-    for (int i = 0; i < N; ++i) maxd = dmaxd2(maxd, fabs(W[i][i]));
+    for (int i = 0; i < N; ++i) maxd = dmaxd(maxd, fabs(W[i][i]));
     bool finished = false;
     for (int sweep = 0; !finished && sweep < 100; ++sweep) {
       finished = true;
@@ -1788,7 +1772,7 @@ __device__ inline void quad_solve(const DScene& s, const FilterDev& F, const dou
       for (int pp = 1; pp < N; ++pp)
 #pragma unroll
         for (int q = 0; q < pp; ++q) {
-          const double thr = dmaxd2(dmin, 2.0 * eps * maxd);
+          const double thr = dmaxd(dmin, 2.0 * eps * maxd);
           if (!(fabs(W[pp][q]) > thr || fabs(W[q][pp]) > thr)) continue;
           finished = false;
           double m00 = W[pp][pp], m01 = W[pp][q], m10 = W[q][pp], m11 = W[q][q];
@@ -1842,7 +1826,7 @@ __device__ inline void quad_solve(const DScene& s, const FilterDev& F, const dou
             V[i][pp] = cr * xp - sr * xq;
             V[i][q] = sr * xp + cr * xq;
           }
-          maxd = dmaxd2(maxd, dmaxd2(fabs(W[pp][pp]), fabs(W[q][q])));
+          maxd = dmaxd(maxd, dmaxd(fabs(W[pp][pp]), fabs(W[q][q])));
         }
     }
     // ---- singular values, signs, scale; sorted descending (selection, unrolled: register arrays)
@@ -1887,7 +1871,7 @@ __device__ inline void quad_solve(const DScene& s, const FilterDev& F, const dou
     }
     int rank = 0;
     if (nonzero > 0) {
-      const double pre = dmaxd2(sv[0] * (N * eps), dmin);
+      const double pre = dmaxd(sv[0] * (N * eps), dmin);
       int i = nonzero - 1;
 #pragma unroll
       for (int c = N - 1; c >= 0; --c)
@@ -1981,11 +1965,11 @@ __global__ __launch_bounds__(64) void quad_qr_kernel(QuadJobs qj, const unsigned
       const double a[5] = {(double)(fx * fx), (double)(fy * fy), (double)(fx * fy), (double)fx, (double)fy};
       for (int j = 0; j < N; ++j) {
         A[6 * i + j] = a[j];
-        smax = dmaxd2(smax, fabs(a[j]));  // the max of the non-NaN terms: any order gives it
+        smax = dmaxd(smax, fabs(a[j]));  // the max of the non-NaN terms: any order gives it
       }
       A[6 * i + 5] = (double)gz[i];
     }
-    for (int m = 1; m < QL; m <<= 1) smax = dmaxd2(smax, __shfl_xor(smax, m));
+    for (int m = 1; m < QL; m <<= 1) smax = dmaxd(smax, __shfl_xor(smax, m));
     const bool fin = isfinite(smax);
     const double scale = smax == 0.0 ? 1.0 : smax;
     const int nn = fin ? n : 0;  // the rows this job's QR walks (none: x = 0, as quad_lane_job)
@@ -2749,29 +2733,21 @@ static void dbg(hipStream_t st, const char* what) {
   fflush(stderr);
 }
 
-template <class T>
-static hipError_t dalloc(T*& p, size_t n) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  const hipError_t e = hipMalloc((void**)&p, (n ? n : 1) * sizeof(T));
-  if (e == hipSuccess) poison_alloc(p, (n ? n : 1) * sizeof(T));
-  return e;
+// hipcub's two calls: the size query, `temp` grown to it when it is short (to exactly the size, or
+// with `doubling` to max(size, 2 x its capacity)), then the run.  call(void* temp, size_t& bytes).
+// At the FilterBuffers sites reserve() / ensure_entries() have sized B.temp for every sort and scan
+// beforehand, so the query (host only) finds it large enough; were it not, it grows here.
+template <class Call>
+static hipError_t cub_run(DevBuf<char>& temp, Call&& call, bool doubling = false) {
+  size_t tb = 0;
+  FCHK(call(nullptr, tb));
+  if (tb > temp.cap || !temp.p) FCHK(temp.alloc(doubling ? std::max(tb, 2 * temp.cap) : tb));
+  tb = temp.cap;
+  return call(temp.p, tb);
 }
 
-FilterBuffers::~FilterBuffers() {
-  void* ps[] = {preg, vreg, tgoff, cnt, off, keys, keys2, cellcnt, pg_off, pg_items, vp_off, vp_items, dpkey,
-                order, rank, hot, flags, safe, need, list, scratch, counters, temp, edge_off, edges, rbits, coordc,
-                qf, qrows, qjobs, qctr, qkeys, qkeys2, qcrows, qoff, vrows, used, normalc, refpos, xr, ovf_items,
-                scratch_big};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-}
-
-void FilterBuffers::release() {
-  this->~FilterBuffers();
-  new (this) FilterBuffers();
-}
-
+// Every buffer of reserve() is allocated anew (exactly, contents discarded) whenever a logical
+// capacity grows.
 hipError_t FilterBuffers::reserve(int n_, long long ncells_, int tnum_, int grid_) {
   if (n_ <= cap_n && ncells_ <= cap_cells && grid_ <= cap_grid) return hipSuccess;
   // 25 % headroom: the next loop iteration's expansion reserves its model plus a few waves, so an exact
@@ -2782,69 +2758,49 @@ hipError_t FilterBuffers::reserve(int n_, long long ncells_, int tnum_, int grid
   // cell-list entries: about 16 per patch to start with (a C3 patch registers ~10-17), grown by
   // ensure_entries to what build_lists counts -- not cap_n x PMVS_MAX_IMAGES
   cap_e = std::max(cap_e, (size_t)cap_n * 16);
-  cap_pi = cap_vi = cap_e;
   const size_t ne = cap_e;
-  FCHK(dalloc(preg, cap_n)); FCHK(dalloc(vreg, cap_n)); FCHK(dalloc(tgoff, PMVS_MAX_TARGETS + 1));
-  FCHK(dalloc(cnt, cap_n + 1)); FCHK(dalloc(off, cap_n + 1));
-  FCHK(dalloc(keys, std::max(ne, (size_t)cap_n))); FCHK(dalloc(keys2, std::max(ne, (size_t)cap_n)));
-  FCHK(dalloc(cellcnt, cap_cells + 1)); FCHK(dalloc(pg_off, cap_cells + 1)); FCHK(dalloc(vp_off, cap_cells + 1));
-  FCHK(dalloc(pg_items, ne)); FCHK(dalloc(vp_items, ne)); FCHK(dalloc(dpkey, cap_cells));
-  FCHK(dalloc(coordc, cap_n));
-  FCHK(dalloc(order, cap_n)); FCHK(dalloc(rank, cap_n)); FCHK(dalloc(hot, cap_n)); FCHK(dalloc(flags, cap_n));
-  FCHK(dalloc(safe, cap_n)); FCHK(dalloc(need, cap_n)); FCHK(dalloc(list, cap_n));
-  FCHK(dalloc(scratch, (size_t)cap_grid * NB_SCR)); FCHK(dalloc(counters, 16));
-  FCHK(dalloc(edge_off, cap_n + 1));
+  FCHK(preg.alloc(cap_n)); FCHK(vreg.alloc(cap_n)); FCHK(tgoff.alloc(PMVS_MAX_TARGETS + 1));
+  FCHK(cnt.alloc(cap_n + 1)); FCHK(off.alloc(cap_n + 1));
+  FCHK(keys.alloc(std::max(ne, (size_t)cap_n))); FCHK(keys2.alloc(std::max(ne, (size_t)cap_n)));
+  FCHK(cellcnt.alloc(cap_cells + 1)); FCHK(pg_off.alloc(cap_cells + 1)); FCHK(vp_off.alloc(cap_cells + 1));
+  FCHK(pg_items.alloc(ne)); FCHK(vp_items.alloc(ne)); FCHK(dpkey.alloc(cap_cells));
+  FCHK(coordc.alloc(cap_n));
+  FCHK(order.alloc(cap_n)); FCHK(rank.alloc(cap_n)); FCHK(hot.alloc(cap_n)); FCHK(flags.alloc(cap_n));
+  FCHK(safe.alloc(cap_n)); FCHK(need.alloc(cap_n)); FCHK(list.alloc(cap_n));
+  FCHK(scratch.alloc((size_t)cap_grid * NB_SCR)); FCHK(counters.alloc(16));
+  FCHK(edge_off.alloc(cap_n + 1));
   // deferred filterQuad fits: up to 48 rows per patch on average, at most 2^27 rows (7.5 GB);
   // patches past the capacity are fitted in neighbor_kernel itself
   // quad_lane_kernel's row pool: jobs sorted by descending n, so the 64-lane chunks' rows
   // (64 x their first n) sum to at most every job's n plus 64 x NB_CAP
   cap_qrows = std::min((size_t)cap_n * 48, (size_t)1 << 27);
-  FCHK(dalloc(qf, cap_qrows * 3)); FCHK(dalloc(qrows, (cap_qrows + 64 * (size_t)NB_CAP) * 6)); FCHK(dalloc(qjobs, cap_n));
-  FCHK(dalloc(qctr, 3)); FCHK(dalloc(qkeys, cap_n)); FCHK(dalloc(qkeys2, cap_n));
-  FCHK(dalloc(qcrows, cap_n / 64 + 2)); FCHK(dalloc(qoff, cap_n / 64 + 2));
+  FCHK(qf.alloc(cap_qrows * 3)); FCHK(qrows.alloc((cap_qrows + 64 * (size_t)NB_CAP) * 6)); FCHK(qjobs.alloc(cap_n));
+  FCHK(qctr.alloc(3)); FCHK(qkeys.alloc(cap_n)); FCHK(qkeys2.alloc(cap_n));
+  FCHK(qcrows.alloc(cap_n / 64 + 2)); FCHK(qoff.alloc(cap_n / 64 + 2));
   size_t t1 = 0, t2 = 0;
-  FCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, keys, keys2, (int)ne));
-  FCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, cellcnt, pg_off, (int)(cap_cells + 1)));
+  FCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, keys.p, keys2.p, (int)ne));
+  FCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, cellcnt.p, pg_off.p, (int)(cap_cells + 1)));
   size_t t3 = 0;
-  FCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, cnt, off, cap_n + 1));
+  FCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, cnt.p, off.p, cap_n + 1));
   size_t t4 = 0;
-  FCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, t4, qkeys, qkeys2, cap_n, 0, 43));
-  temp_bytes = std::max(std::max(t1, t4), std::max(t2, t3));
-  if (temp) (void)hipFree(temp);
-  temp = nullptr;
-  FCHK(hipMalloc(&temp, temp_bytes ? temp_bytes : 1));
+  FCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, t4, qkeys.p, qkeys2.p, cap_n, 0, 43));
+  FCHK(temp.alloc(std::max(std::max(t1, t4), std::max(t2, t3))));
   return hipSuccess;
 }
 
 // Grows the cell-list entry buffers (and the sort's temp storage) to e entries; the other per-patch
 // buffers keep their size.
 hipError_t FilterBuffers::ensure_entries(size_t e, int vis) {
-  size_t& ci = vis ? cap_vi : cap_pi;
-  if (e > ci) {  // only the list being built: the other one's items stay valid
-    ci = std::max(e, ci + ci / 2);
-    FCHK(dalloc(vis ? vp_items : pg_items, ci));
-  }
+  DevBuf<int>& items = vis ? vp_items : pg_items;
+  // only the list being built: the other one's items stay valid
+  if (e > items.cap) FCHK(items.alloc(std::max(e, items.cap + items.cap / 2)));
   if (e <= cap_e) return hipSuccess;
   cap_e = std::max(e, cap_e + cap_e / 2);
   const size_t ne = std::max(cap_e, (size_t)cap_n);
-  FCHK(dalloc(keys, ne)); FCHK(dalloc(keys2, ne));
+  FCHK(keys.alloc(ne)); FCHK(keys2.alloc(ne));
   size_t t1 = 0;
-  FCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, keys, keys2, (int)ne));
-  if (t1 > temp_bytes) {
-    if (temp) (void)hipFree(temp);
-    temp = nullptr;
-    temp_bytes = t1;
-    FCHK(hipMalloc(&temp, temp_bytes));
-  }
-  return hipSuccess;
-}
-
-template <class T>
-static hipError_t fgrow(T*& p, size_t& cap, size_t need) {  // grown, contents not kept
-  if (need <= cap && p) return hipSuccess;
-  need = std::max(need, cap + cap / 4);
-  FCHK(dalloc(p, need));
-  cap = need;
+  FCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, keys.p, keys2.p, (int)ne));
+  if (t1 > temp.cap) FCHK(temp.alloc(t1));
   return hipSuccess;
 }
 
@@ -2852,8 +2808,8 @@ static hipError_t fgrow(T*& p, size_t& cap, size_t need) {  // grown, contents n
 // B.ovf_items (count at B.counters[10]); the NB_CAP_BIG form, launched right after it without a host
 // sync (its workgroups leave at once when the list is empty), walks them (queue B.counters[11]).
 static hipError_t nb_overflow_lists(FilterBuffers& B, size_t items, hipStream_t st, NbOverflow& walk, NbOverflow& rewalk) {
-  FCHK(fgrow(B.ovf_items, B.cap_ovf, std::max<size_t>(items, 1)));
-  if (!B.scratch_big) FCHK(hipMalloc((void**)&B.scratch_big, (size_t)NB_GRID_BIG * NB_CAP_BIG * 8 * sizeof(double)));
+  FCHK(B.ovf_items.grow_headroom(std::max<size_t>(items, 1)));
+  if (!B.scratch_big) FCHK(B.scratch_big.alloc((size_t)NB_GRID_BIG * NB_CAP_BIG * 8));
   FCHK(hipMemsetAsync(B.counters + 10, 0, 2 * sizeof(int), st));
   walk = NbOverflow{};
   walk.items = B.ovf_items;
@@ -2919,7 +2875,7 @@ constexpr size_t kGatherBytes = 1024;  // per item (whole 4-byte words)
 // leave nothing behind.
 struct D2HStage {
   PinnedBuf pin;
-  unsigned* dgather = nullptr;
+  DevBuf<unsigned> dgather;
 };
 static std::mutex g_stage_mu;
 static std::unordered_map<hipStream_t, D2HStage*> g_stages;
@@ -2939,8 +2895,7 @@ void d2h_stage_release(hipStream_t st) {
     p = it->second;
     g_stages.erase(it);
   }
-  if (p->dgather) (void)hipFree(p->dgather);
-  delete p;  // PinnedBuf frees the pinned buffer
+  delete p;  // its members free the pinned buffer and the gather buffer
 }
 namespace {
 struct GatherArgs {
@@ -2968,7 +2923,7 @@ static hipError_t d2h_sync(hipStream_t st, std::initializer_list<D2H> reads) {
   PinnedBuf& pb = sg.pin;
   if (tot) FCHK(pb.ensure(tot));
   if (gatherable && small > 1 && small <= kGatherMax) {  // every read small: one kernel, one copy
-    if (!sg.dgather) FCHK(hipMalloc((void**)&sg.dgather, kGatherMax * kGatherBytes));
+    if (!sg.dgather) FCHK(sg.dgather.alloc(kGatherMax * kGatherBytes / sizeof(unsigned)));
     unsigned* const dstage = sg.dgather;
     GatherArgs a{};
     size_t o = 0;
@@ -3029,8 +2984,7 @@ static hipError_t build_lists(Ctx& c, int vis) {
   int* items = vis ? B.vp_items : B.pg_items;
   hipLaunchKernelGGL(count_entries_kernel, dim3(nblk(c.n)), dim3(256), 0, c.st, c.P, c.n, reg, vis, B.cnt);
   FCHK(hipMemsetAsync(B.cnt + c.n, 0, sizeof(int), c.st));
-  size_t tb = B.temp_bytes;
-  FCHK(hipcub::DeviceScan::ExclusiveSum(B.temp, tb, B.cnt, B.off, c.n + 1, c.st));
+  FCHK(cub_run(B.temp, [&](void* t, size_t& tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, B.cnt.p, B.off.p, c.n + 1, c.st); }));
   int e = 0;
   FCHK(read_int(B.off + c.n, &e, c.st));
   (vis ? c.nvp : c.npg) = e;
@@ -3038,15 +2992,18 @@ static hipError_t build_lists(Ctx& c, int vis) {
   items = vis ? B.vp_items : B.pg_items;  // (re)allocated by ensure_entries
   hipLaunchKernelGGL(emit_entries_kernel, dim3(nblk((long long)c.n * kLG)), dim3(256), 0, c.st, c.s, c.P, c.n, reg, vis, B.off, B.tgoff,
                      B.keys);
-  tb = B.temp_bytes;
-  if (e > 0) FCHK(hipcub::DeviceRadixSort::SortKeys(B.temp, tb, B.keys, B.keys2, e, 32, 32 + cell_bits(c.ncells), c.st));
+  if (e > 0)
+    FCHK(cub_run(B.temp, [&](void* t, size_t& tb) {
+      return hipcub::DeviceRadixSort::SortKeys(t, tb, B.keys.p, B.keys2.p, e, 32, 32 + cell_bits(c.ncells), c.st);
+    }));
   FCHK(memset_big(B.cellcnt, 0, (c.ncells + 1) * sizeof(int), c.st));
   if (e > 0) {
     hipLaunchKernelGGL(cell_hist_kernel, dim3(nblk(e)), dim3(256), 0, c.st, B.keys2, e, B.cellcnt);
     hipLaunchKernelGGL(items_kernel, dim3(nblk(e)), dim3(256), 0, c.st, B.keys2, e, items);
   }
-  tb = B.temp_bytes;
-  FCHK(hipcub::DeviceScan::ExclusiveSum(B.temp, tb, B.cellcnt, csr_off, (int)(c.ncells + 1), c.st));
+  FCHK(cub_run(B.temp, [&](void* t, size_t& tb) {
+    return hipcub::DeviceScan::ExclusiveSum(t, tb, B.cellcnt.p, csr_off, (int)(c.ncells + 1), c.st);
+  }));
   return hipGetLastError();
 }
 
@@ -3139,8 +3096,9 @@ static hipError_t collect(Ctx& c) {
   hipLaunchKernelGGL(first_cell_kernel, dim3(std::min(nblk((long long)c.n * kLG), 2048u)), dim3(256), 0, c.st, c.s, c.P, c.n,
                      B.preg, B.tgoff, B.keys,
                      B.counters);
-  size_t tb = B.temp_bytes;
-  FCHK(hipcub::DeviceRadixSort::SortKeys(B.temp, tb, B.keys, B.keys2, c.n, 32, 32 + cell_bits(c.ncells), c.st));
+  FCHK(cub_run(B.temp, [&](void* t, size_t& tb) {
+    return hipcub::DeviceRadixSort::SortKeys(t, tb, B.keys.p, B.keys2.p, c.n, 32, 32 + cell_bits(c.ncells), c.st);
+  }));
   FCHK(read_int(B.counters, &c.nalive, c.st));
   FCHK(hipMemsetAsync(B.rank, 0xff, c.n * sizeof(int), c.st));
   if (c.nalive > 0)
@@ -3172,9 +3130,9 @@ static hipError_t set_dm_vgrids(Ctx& c, int additive) {
     const long long row_words = (c.nalive + 63) / 64;
     const int nown_max = (c.s.tnum + c.world - 1) / c.world;
     const size_t rwords = (size_t)nown_max * row_words;
-    FCHK(fgrow(B.normalc, B.cap_normalc, (size_t)c.nalive));
-    FCHK(fgrow(B.used, B.cap_used, (size_t)c.nalive * (PMVS_MAX_TARGETS / 64)));
-    FCHK(fgrow(B.vrows, B.cap_vrows, rwords));
+    FCHK(B.normalc.grow_headroom((size_t)c.nalive));
+    FCHK(B.used.grow_headroom((size_t)c.nalive * (PMVS_MAX_TARGETS / 64)));
+    FCHK(B.vrows.grow_headroom(rwords));
     hipLaunchKernelGGL(normalc_kernel, dim3(nblk(c.nalive)), dim3(256), 0, c.st, c.P, B.order, c.nalive, B.normalc);
     hipLaunchKernelGGL(used_kernel, dim3(nblk((long long)c.nalive * kLG)), dim3(256), 0, c.st, c.s, c.dev(), additive, B.used);
     if (nown > 0)
@@ -3183,9 +3141,9 @@ static hipError_t set_dm_vgrids(Ctx& c, int additive) {
                          B.coordc, B.normalc, B.used, c.rank, c.world, nown, row_words, B.vrows);
     const unsigned long long* rows = B.vrows;
     if (c.world > 1) {
-      FCHK(fgrow(B.xr, B.cap_xr, rwords * 8 * c.world));
+      FCHK(B.xr.grow_headroom(rwords * 8 * c.world));
       FCHK(c.xchg(0, B.vrows, rwords * 8, B.xr, nullptr));
-      rows = reinterpret_cast<const unsigned long long*>(B.xr);
+      rows = reinterpret_cast<const unsigned long long*>(B.xr.p);
     }
     hipLaunchKernelGGL(vis_lists_kernel, dim3(xcd_grid(c.nalive)), dim3(256), 0, c.st, c.s, c.dev(), additive, c.world,
                        nown_max, row_words, rows, B.vreg);
@@ -3274,12 +3232,12 @@ static hipError_t filter_pass_impl(const DScene& s, FilterBuffers& B, pmvs_patch
   // flags[0, n) of the patches this rank decided -> every rank's, OR-merged (one exchange)
   auto merge_flags = [&](int value, long long* vsum) -> hipError_t {
     const size_t nw = (size_t)(n + 31) / 32;
-    FCHK(fgrow(B.rbits, B.cap_rbits, nw + 1));
-    FCHK(fgrow(B.xr, B.cap_xr, (nw + 1) * 4 * G));
+    FCHK(B.rbits.grow_headroom(nw + 1));
+    FCHK(B.xr.grow_headroom((nw + 1) * 4 * G));
     if (nw) hipLaunchKernelGGL(pack_bits_kernel, dim3(nblk((long long)nw)), dim3(256), 0, st, B.flags, n, B.rbits);
     FCHK(c.xchg(value, B.rbits, nw * 4, B.xr, vsum));
     if (nw) {
-      hipLaunchKernelGGL(or_bits_kernel, dim3(nblk((long long)nw)), dim3(256), 0, st, reinterpret_cast<const unsigned*>(B.xr),
+      hipLaunchKernelGGL(or_bits_kernel, dim3(nblk((long long)nw)), dim3(256), 0, st, reinterpret_cast<const unsigned*>(B.xr.p),
                          G, nw, B.rbits);
       hipLaunchKernelGGL(unpack_bits_kernel, dim3(nblk(n)), dim3(256), 0, st, B.rbits, n, B.flags);
     }
@@ -3304,10 +3262,10 @@ static hipError_t filter_pass_impl(const DScene& s, FilterBuffers& B, pmvs_patch
   hipLaunchKernelGGL(exact_entries_kernel, dim3(nblk(ncells)), dim3(256), 0, st, s, c.dev(), ncells, B.safe, R, G);
   if (part) {  // safe bits of every rank's targets, OR-merged
     const size_t words = (size_t)n * (sizeof(Reg) / 4);
-    FCHK(fgrow(B.xr, B.cap_xr, words * 4 * G));
+    FCHK(B.xr.grow_headroom(words * 4 * G));
     FCHK(c.xchg(0, B.safe, words * 4, B.xr, nullptr));
-    hipLaunchKernelGGL(or_bits_kernel, dim3(nblk((long long)words)), dim3(256), 0, st, reinterpret_cast<const unsigned*>(B.xr), G,
-                       words, reinterpret_cast<unsigned*>(B.safe));
+    hipLaunchKernelGGL(or_bits_kernel, dim3(nblk((long long)words)), dim3(256), 0, st, reinterpret_cast<const unsigned*>(B.xr.p), G,
+                       words, reinterpret_cast<unsigned*>(B.safe.p));
   }
   FCHK(hipMemsetAsync(B.need, 0, n * sizeof(int), st));
   if (c.nalive)
@@ -3323,17 +3281,16 @@ static hipError_t filter_pass_impl(const DScene& s, FilterBuffers& B, pmvs_patch
     if (na > 0) {
       hipLaunchKernelGGL(flag_order_kernel, dim3(nblk(na)), dim3(256), 0, st, B.need, B.order, na, B.cnt);
       FCHK(hipMemsetAsync(B.cnt + na, 0, sizeof(int), st));
-      size_t tb = B.temp_bytes;
-      FCHK(hipcub::DeviceScan::ExclusiveSum(B.temp, tb, B.cnt, B.off, na + 1, st));
+      FCHK(cub_run(B.temp, [&](void* t, size_t& tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, B.cnt.p, B.off.p, na + 1, st); }));
       hipLaunchKernelGGL(scatter_order_kernel, dim3(nblk(na)), dim3(256), 0, st, B.cnt, B.off, B.order, na, B.list);
       FCHK(read_int(B.off + na, &m, st));
     }
     if (part) {  // the owners' setRefImage outcomes (m is the same on every rank)
-      FCHK(fgrow(B.refpos, B.cap_refpos, (size_t)std::max(m, 1)));
-      FCHK(fgrow(B.xr, B.cap_xr, (size_t)std::max(m, 1) * 4 * G));
+      FCHK(B.refpos.grow_headroom((size_t)std::max(m, 1)));
+      FCHK(B.xr.grow_headroom((size_t)std::max(m, 1) * 4 * G));
       FCHK(launch_filter_refimage(s, dP, B.list, m, grid, st, B.refpos, R, G));
       FCHK(c.xchg(0, B.refpos, (size_t)m * 4, B.xr, nullptr));
-      FCHK(launch_apply_refpos(s, dP, B.list, m, reinterpret_cast<const int*>(B.xr), G, st));
+      FCHK(launch_apply_refpos(s, dP, B.list, m, reinterpret_cast<const int*>(B.xr.p), G, st));
     } else if (m) {
       FCHK(launch_filter_refimage(s, dP, B.list, m, grid, st));
     }
@@ -3366,11 +3323,11 @@ static hipError_t filter_pass_impl(const DScene& s, FilterBuffers& B, pmvs_patch
       if (nj > 0) {
         const int nch = (nj + 63) / 64;
         hipLaunchKernelGGL(quad_keys_kernel, dim3(nblk(nj)), dim3(256), 0, st, B.qjobs, nj, B.qkeys);
-        size_t tb = B.temp_bytes;
-        FCHK(hipcub::DeviceRadixSort::SortKeys(B.temp, tb, B.qkeys, B.qkeys2, nj, 0, 43, st));
+        FCHK(cub_run(B.temp, [&](void* t, size_t& tb) {
+          return hipcub::DeviceRadixSort::SortKeys(t, tb, B.qkeys.p, B.qkeys2.p, nj, 0, 43, st);
+        }));
         hipLaunchKernelGGL(quad_chunk_rows_kernel, dim3(nblk(nch)), dim3(256), 0, st, B.qkeys2, nj, B.qcrows);
-        tb = B.temp_bytes;
-        FCHK(hipcub::DeviceScan::ExclusiveSum(B.temp, tb, B.qcrows, B.qoff, nch, st));
+        FCHK(cub_run(B.temp, [&](void* t, size_t& tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, B.qcrows.p, B.qoff.p, nch, st); }));
         int dev = 0, cus = 0;
         FCHK(hipGetDevice(&dev));
         FCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -3441,16 +3398,10 @@ static hipError_t filter_pass_impl(const DScene& s, FilterBuffers& B, pmvs_patch
     const int na = c.nalive;
     hipLaunchKernelGGL(group_edges_kernel, dim3(nblk(na)), dim3(256), 0, st, s, c.dev(), 0, B.edge_off, B.cnt, B.edges);
     FCHK(hipMemsetAsync(B.cnt + na, 0, sizeof(int), st));
-    size_t tb = B.temp_bytes;
-    FCHK(hipcub::DeviceScan::ExclusiveSum(B.temp, tb, B.cnt, B.edge_off, na + 1, st));
+    FCHK(cub_run(B.temp, [&](void* t, size_t& tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, B.cnt.p, B.edge_off.p, na + 1, st); }));
     int ne = 0;
     FCHK(read_int(B.edge_off + na, &ne, st));
-    if ((size_t)ne > B.edges_cap) {
-      if (B.edges) (void)hipFree(B.edges);
-      B.edges = nullptr;
-      B.edges_cap = (size_t)ne * 2;
-      FCHK(hipMalloc((void**)&B.edges, B.edges_cap * sizeof(int)));
-    }
+    if ((size_t)ne > B.edges.cap) FCHK(B.edges.alloc((size_t)ne * 2));
     hipLaunchKernelGGL(group_edges_kernel, dim3(nblk(na)), dim3(256), 0, st, s, c.dev(), 1, B.edge_off, B.cnt, B.edges);
     // filterSmallGroups' labelling (filter.cpp:520-562): a BFS from every unlabelled patch in
     // collect order over the directed neighbour edges.  The label it gives patch j is the
@@ -3722,78 +3673,7 @@ __global__ void alive_reg_kernel(int n, const int* __restrict__ alive, Reg* __re
   }
 }
 
-// Host mirror of one target cell during an expansion run.
-struct HostCell {
-  unsigned char count, occ;
-};
-static_assert(sizeof(HostCell) == 2, "HostCell layout");
-struct HostCells {  // 2 MB-aligned, transparent huge pages: the commit's accesses are random
-  HostCell* p = nullptr;
-  explicit HostCells(size_t n) {
-    const size_t bytes = ((n * sizeof(HostCell)) + (2u << 20) - 1) & ~((size_t)(2u << 20) - 1);
-    p = static_cast<HostCell*>(aligned_alloc(2u << 20, bytes ? bytes : (2u << 20)));
-    if (p) (void)madvise(p, bytes, MADV_HUGEPAGE);
-  }
-  ~HostCells() { free(p); }
-};
-
-// {count 0, occupied = pgrids holds a patch} per cell, for the host mirror.
-__global__ void cell_init_kernel(const int* __restrict__ pg_off, long long ncells, HostCell* __restrict__ out) {
-  const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c < ncells) out[c] = HostCell{0, (unsigned char)(pg_off[c + 1] > pg_off[c] ? 1 : 0)};
-}
-
-// CExpand::updateCounts results of one commit (host-computed): counts[cell] = value.
-__global__ void counts_scatter_kernel(const int* __restrict__ cells, const unsigned char* __restrict__ vals, int n,
-                                      unsigned char* __restrict__ counts) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < n) counts[cells[k]] = vals[k];
-}
-
-template <class T>
-static hipError_t grow(T*& p, size_t& cap, size_t need) {
-  if (need <= cap && p) return hipSuccess;
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  cap = need;
-  const hipError_t e = hipMalloc((void**)&p, (need ? need : 1) * sizeof(T));
-  if (e == hipSuccess) poison_alloc(p, (need ? need : 1) * sizeof(T));
-  return e;
-}
-
 }  // namespace
-
-void delete_commit_work(CommitWork* w);  // after CommitWork's definition
-ExpandBuffers::~ExpandBuffers() {
-  void* ps[] = {parents, cand_coord, cand_ok, cand, prep, status, slots, cand2, prep2, res, outp, ostatus, counts, alive,
-                pg_head, vp_head, d_ent, pool_used, tcells, tvals, qtmp, crec, acc, dupd, cellinit, occ,
-                qkey, qrank, qrank2, qsort_tmp, xsd, xrd, cidx, qkeep, qpos, qitems, sflag, spos, slot2};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  delete_commit_work(cm);
-}
-
-void ExpandBuffers::release() {
-  this->~ExpandBuffers();
-  new (this) ExpandBuffers();
-}
-
-// Grows a device array keeping its contents (the delta-chain entry pool, the per-patch arrays).
-// 1.5x: old and new coexist during the copy, and at C5 scale the model alone is ~80 GB.
-template <class T>
-static hipError_t grow_keep(T*& p, size_t& cap, size_t need, size_t used, hipStream_t st) {
-  if (need <= cap && p) return hipSuccess;
-  const size_t ncap = std::max(need, cap + cap / 2 + 1024);
-  T* q = nullptr;
-  FCHK(hipMalloc((void**)&q, ncap * sizeof(T)));
-  poison_alloc(q, ncap * sizeof(T));
-  if (p && used) FCHK(hipMemcpyAsync(q, p, used * sizeof(T), hipMemcpyDeviceToDevice, st));
-  FCHK(hipStreamSynchronize(st));
-  if (p) (void)hipFree(p);
-  p = q;
-  cap = ncap;
-  return hipSuccess;
-}
 
 // ============================================================================ device commit
 // CExpand's commit of a wave (expand.cpp:225-266 addPatch + checkCounts, :309-406 updateCounts) in
@@ -3805,24 +3685,17 @@ static hipError_t grow_keep(T*& p, size_t& cap, size_t need, size_t used, hipStr
 // the first undecided candidate, and decides every candidate that is first in all of its cells
 // (so each cell has one writer per round and plain stores suffice).  The result is the
 // sequential commit exactly, in as many rounds as the longest chain of cell-sharing candidates.
+// Its buffers are sized by the wave's candidates (cap_k) or by their cell accesses (cap_a), doubled
+// when short, contents discarded.
 struct CommitWork {
-  int *stc = nullptr, *nacc = nullptr, *aoff = nullptr, *vals = nullptr, *vals2 = nullptr, *pos = nullptr,
-      *head = nullptr, *segid = nullptr, *seghead = nullptr, *segptr = nullptr, *segfirst = nullptr,
-      *slot2 = nullptr, *flag = nullptr, *scan = nullptr, *ctr = nullptr, *pbits = nullptr;
-  unsigned long long *keys = nullptr, *keys2 = nullptr;
-  unsigned char* dec = nullptr;
-  int2* push = nullptr;
-  void* temp = nullptr;
-  size_t cap_k = 0, cap_a = 0, temp_bytes = 0;
-  ~CommitWork() {
-    void* ps[] = {stc, nacc, aoff, vals, vals2, pos, head, segid, seghead, segptr, segfirst, slot2, flag, scan, ctr,
-                  pbits, keys, keys2, dec, push, temp};
-    for (void* p : ps)
-      if (p) (void)hipFree(p);
-  }
+  DevBuf<int> stc, nacc, aoff, vals, vals2, pos, head, segid, seghead, segptr, segfirst, flag, scan, ctr, pbits;
+  DevBuf<unsigned long long> keys, keys2;
+  DevBuf<unsigned char> dec;
+  DevBuf<int2> push;
+  DevBuf<char> temp;  // hipcub temp storage
+  size_t cap_k = 0, cap_a = 0;
 };
-
-void delete_commit_work(CommitWork* w) { delete w; }
+void CommitWorkDelete::operator()(CommitWork* w) const { delete w; }
 
 // occupancy per target cell after the model load: pgrids holds a patch
 __global__ void occ_init_kernel(const int* __restrict__ pg_off, long long ncells, unsigned char* __restrict__ occ) {
@@ -4147,15 +4020,6 @@ __global__ void cm_serial_kernel(DScene s, const int* __restrict__ status, const
       if (bits[pi]) P[parents[pi]].dflag |= bits[pi];
 }
 
-template <class T>
-static hipError_t cm_grow(T*& p, size_t n) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  const hipError_t e = hipMalloc((void**)&p, (n ? n : 1) * sizeof(T));
-  if (e == hipSuccess) poison_alloc(p, (n ? n : 1) * sizeof(T));
-  return e;
-}
-
 struct CommitOut {
   int nacc = 0, pbits = 0;
   long long entries = 0, fail[4] = {0, 0, 0, 0};  // fail_prep, fail_pre, fail_post, fail_commit
@@ -4169,21 +4033,21 @@ static hipError_t device_commit(const DScene& s, ExpandBuffers& X, hipStream_t s
                                 const int* d_ovf, int* ovf,
                                 int cthr, bool check, int first, long long pool0, bool apply_dflag, pmvs_patch* dP,
                                 CommitOut& out) {
-  if (!X.cm) X.cm = new CommitWork();
+  if (!X.cm) X.cm.reset(new CommitWork());
   CommitWork& W = *X.cm;
   const int nk = np * 6;
   if ((size_t)nk + 1 > W.cap_k) {
     const size_t c = std::max((size_t)nk + 1, 2 * W.cap_k);
-    FCHK(cm_grow(W.stc, c)); FCHK(cm_grow(W.nacc, c)); FCHK(cm_grow(W.aoff, c));
-    FCHK(cm_grow(W.flag, c)); FCHK(cm_grow(W.scan, 6 * c)); FCHK(cm_grow(W.dec, c)); FCHK(cm_grow(W.pbits, c));
-    FCHK(cm_grow(W.push, c));
+    FCHK(W.stc.alloc(c)); FCHK(W.nacc.alloc(c)); FCHK(W.aoff.alloc(c));
+    FCHK(W.flag.alloc(c)); FCHK(W.scan.alloc(6 * c)); FCHK(W.dec.alloc(c)); FCHK(W.pbits.alloc(c));
+    FCHK(W.push.alloc(c));
     W.cap_k = c;
   }
-  if (!W.ctr) FCHK(cm_grow(W.ctr, 9 + 2 * kSerialCommit));
+  if (!W.ctr) FCHK(W.ctr.alloc(9 + 2 * kSerialCommit));
   const int* slot2v = d_slot2;  // candidate -> survivor (surv_scatter_kernel)
   *ovf = 0;
   if (nk <= kSerialCommit) {
-    FCHK(grow(X.acc, X.cap_acc, 2 * (size_t)nk));
+    FCHK(X.acc.grow(2 * (size_t)nk));
     hipLaunchKernelGGL(cm_serial_kernel, dim3(1), dim3(64), 0, st, s, X.status, slot2v, X.crec, nk, np, X.counts, X.occ,
                        cthr, check ? 1 : 0, first, (int)pool0, X.acc, W.ctr, X.parents, dP, apply_dflag ? 1 : 0);
     int h[9 + 2 * kSerialCommit];
@@ -4205,16 +4069,9 @@ static hipError_t device_commit(const DScene& s, ExpandBuffers& X, hipStream_t s
   hipLaunchKernelGGL(cm_stage_kernel, dim3(nblk(nk)), dim3(256), 0, st, X.status, slot2v, X.crec, nk, W.stc, W.nacc,
                      W.dec, W.ctr + 6);
   FCHK(hipMemsetAsync(W.nacc + nk, 0, sizeof(int), st));
-  auto temp_need = [&](size_t bytes) -> hipError_t {
-    if (bytes <= W.temp_bytes && W.temp) return hipSuccess;
-    W.temp_bytes = std::max(bytes, 2 * W.temp_bytes);
-    return cm_grow(reinterpret_cast<char*&>(W.temp), W.temp_bytes);
-  };
-  size_t tb = 0;
-  FCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, W.nacc, W.aoff, nk + 1, st));
-  FCHK(temp_need(tb));
-  tb = W.temp_bytes;
-  FCHK(hipcub::DeviceScan::ExclusiveSum(W.temp, tb, W.nacc, W.aoff, nk + 1, st));
+  // W.temp doubles when a sort or scan needs more
+  FCHK(cub_run(W.temp, [&](void* t, size_t& tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, W.nacc.p, W.aoff.p, nk + 1, st); },
+               true));
   int hv[2] = {0, 0};
   FCHK(d2h_sync(st, {{&hv[0], W.aoff + nk, sizeof(int)}, {&hv[1], W.ctr + 6, sizeof(int)},
                      {ovf, d_ovf, d_ovf ? sizeof(int) : 0}}));
@@ -4223,24 +4080,20 @@ static hipError_t device_commit(const DScene& s, ExpandBuffers& X, hipStream_t s
   if (na > 0) {
     if ((size_t)na + 1 > W.cap_a) {
       const size_t c = std::max((size_t)na + 1, 2 * W.cap_a);
-      FCHK(cm_grow(W.keys, c)); FCHK(cm_grow(W.keys2, c)); FCHK(cm_grow(W.vals, c)); FCHK(cm_grow(W.vals2, c));
-      FCHK(cm_grow(W.pos, c)); FCHK(cm_grow(W.head, c)); FCHK(cm_grow(W.segid, c)); FCHK(cm_grow(W.seghead, c));
-      FCHK(cm_grow(W.segptr, c)); FCHK(cm_grow(W.segfirst, c));
+      FCHK(W.keys.alloc(c)); FCHK(W.keys2.alloc(c)); FCHK(W.vals.alloc(c)); FCHK(W.vals2.alloc(c));
+      FCHK(W.pos.alloc(c)); FCHK(W.head.alloc(c)); FCHK(W.segid.alloc(c)); FCHK(W.seghead.alloc(c));
+      FCHK(W.segptr.alloc(c)); FCHK(W.segfirst.alloc(c));
       W.cap_a = c;
     }
     hipLaunchKernelGGL(cm_emit_kernel, dim3(nblk(nk)), dim3(256), 0, st, W.stc, slot2v, X.crec, W.aoff, nk, W.keys,
                        W.vals);
-    tb = 0;
     const int cb = X.ncells > 0 ? 32 + cell_bits(X.ncells) : 64;
-    FCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, W.keys, W.keys2, W.vals, W.vals2, na, 32, cb, st));
-    size_t tb2 = 0;
-    FCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb2, W.head, W.segid, na, st));
-    FCHK(temp_need(std::max(tb, tb2)));
-    tb = W.temp_bytes;
-    FCHK(hipcub::DeviceRadixSort::SortPairs(W.temp, tb, W.keys, W.keys2, W.vals, W.vals2, na, 32, cb, st));
+    FCHK(cub_run(W.temp, [&](void* t, size_t& tb) {
+      return hipcub::DeviceRadixSort::SortPairs(t, tb, W.keys.p, W.keys2.p, W.vals.p, W.vals2.p, na, 32, cb, st);
+    }, true));
     hipLaunchKernelGGL(cm_head_kernel, dim3(nblk(na)), dim3(256), 0, st, W.keys2, W.vals2, na, W.head, W.pos);
-    tb = W.temp_bytes;
-    FCHK(hipcub::DeviceScan::InclusiveSum(W.temp, tb, W.head, W.segid, na, st));
+    FCHK(cub_run(W.temp, [&](void* t, size_t& tb) { return hipcub::DeviceScan::InclusiveSum(t, tb, W.head.p, W.segid.p, na, st); },
+                 true));
     hipLaunchKernelGGL(cm_seg_kernel, dim3(nblk(na)), dim3(256), 0, st, W.head, W.segid, na, W.seghead, W.segptr,
                        W.ctr + 8);  // the segment count stays on the device (cm_first_kernel reads it)
     // W.vals (the sort's input values) is free from here: each access's segment
@@ -4289,11 +4142,8 @@ static hipError_t device_commit(const DScene& s, ExpandBuffers& X, hipStream_t s
     if (decided < nlive && !listed) {
       hipLaunchKernelGGL(cm_undecided_kernel, dim3(nblk(nk)), dim3(256), 0, st, W.dec, nk, uflag);
       FCHK(hipMemsetAsync(uflag + nk, 0, sizeof(int), st));
-      size_t ub = 0;
-      FCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, ub, uflag, upos, nk + 1, st));
-      FCHK(temp_need(ub));
-      ub = W.temp_bytes;
-      FCHK(hipcub::DeviceScan::ExclusiveSum(W.temp, ub, uflag, upos, nk + 1, st));
+      FCHK(cub_run(W.temp, [&](void* t, size_t& tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, uflag, upos, nk + 1, st); },
+                   true));
       hipLaunchKernelGGL(cm_list_kernel, dim3(nblk(nk)), dim3(256), 0, st, uflag, upos, nk, ulist, ucnt);
       listed = true;
     }
@@ -4311,17 +4161,15 @@ static hipError_t device_commit(const DScene& s, ExpandBuffers& X, hipStream_t s
   FCHK(hipMemsetAsync(ia + nk, 0, sizeof(int), st));
   FCHK(hipMemsetAsync(ib + nk, 0, sizeof(int), st));
   FCHK(hipMemsetAsync(ic + nk, 0, sizeof(int), st));
-  tb = 0;
-  FCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, ia, qa, nk + 1, st));
-  FCHK(temp_need(tb));
-  for (int t = 0; t < 3; ++t) {
-    tb = W.temp_bytes;
-    FCHK(hipcub::DeviceScan::ExclusiveSum(W.temp, tb, t == 0 ? ia : t == 1 ? ib : ic, t == 0 ? qa : t == 1 ? qb : qc,
-                                          nk + 1, st));
+  for (int u = 0; u < 3; ++u) {
+    int* in = u == 0 ? ia : u == 1 ? ib : ic;
+    int* sum = u == 0 ? qa : u == 1 ? qb : qc;
+    FCHK(cub_run(W.temp, [&](void* t, size_t& tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, in, sum, nk + 1, st); },
+                 true));
   }
   // accepted / pushed / entries written in k order (the accepted count read on the device), then ONE
   // read of the totals, the counters, the pushes (at most the m survivors) and the parents' bits
-  FCHK(grow(X.acc, X.cap_acc, 2 * (size_t)std::max(m, 1)));
+  FCHK(X.acc.grow(2 * (size_t)std::max(m, 1)));
   hipLaunchKernelGGL(cm_write_kernel, dim3(nblk(nk)), dim3(256), 0, st, W.flag, nk, qa, qb, qc, slot2v, X.crec, (int)pool0,
                      first, X.acc, W.push);
   hipLaunchKernelGGL(cm_bits_kernel, dim3(nblk(np)), dim3(256), 0, st, W.stc, np, W.pbits);
@@ -4422,8 +4270,8 @@ static hipError_t expand_pass_impl(const DScene& s, FilterBuffers& B, ExpandBuff
   }
   FCHK(build_lists(c, 1));
   // ---- registrations committed by this run: per-cell chains (no per-wave rebuild of the CSR)
-  FCHK(grow(X.pg_head, X.cap_pghead, (size_t)ncells));
-  FCHK(grow(X.vp_head, X.cap_vphead, (size_t)ncells));
+  FCHK(X.pg_head.grow((size_t)ncells));
+  FCHK(X.vp_head.grow((size_t)ncells));
   FCHK(memset_big(X.pg_head, 0xff, ncells * sizeof(int), st));
   FCHK(memset_big(X.vp_head, 0xff, ncells * sizeof(int), st));
   size_t pool_need = 0;
@@ -4437,26 +4285,17 @@ static hipError_t expand_pass_impl(const DScene& s, FilterBuffers& B, ExpandBuff
   // The collected patches enter the queue in collect order (seq = collect rank); their max-_tmp
   // order (QCmp: _tmp descending, ties by seq) is a stable descending radix sort on the device.
   const size_t na1 = (size_t)std::max(1, c.nalive);
-  FCHK(grow(X.qtmp, X.cap_qtmp, na1));
-  FCHK(grow(X.qkey, X.cap_qkey, na1));
-  FCHK(grow(X.qrank, X.cap_qrank, na1));
-  FCHK(grow(X.qrank2, X.cap_qrank2, na1));
-  FCHK(grow(X.occ, X.cap_occ, (size_t)ncells));
+  FCHK(X.qtmp.grow(na1));
+  FCHK(X.qkey.grow(na1));
+  FCHK(X.qrank.grow(na1));
+  FCHK(X.qrank2.grow(na1));
+  FCHK(X.occ.grow((size_t)ncells));
   if (c.nalive) {
     hipLaunchKernelGGL(collect_flags_kernel, dim3(nblk(c.nalive)), dim3(256), 0, st, dP, B.order, c.nalive, X.qtmp,
                        X.qrank, B.need);
-    size_t tb = 0;
-    FCHK(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb, X.qtmp, X.qkey, X.qrank, X.qrank2, c.nalive, 0, 32, st));
-    if (tb > X.cap_qsort) {
-      if (X.qsort_tmp) FCHK(hipFree(X.qsort_tmp));
-      X.qsort_tmp = nullptr;
-      X.cap_qsort = 0;
-      FCHK(hipMalloc(&X.qsort_tmp, tb));
-      X.cap_qsort = tb;
-    }
-    tb = X.cap_qsort;
-    FCHK(hipcub::DeviceRadixSort::SortPairsDescending(X.qsort_tmp, tb, X.qtmp, X.qkey, X.qrank, X.qrank2, c.nalive, 0, 32,
-                                                      st));
+    FCHK(cub_run(X.qsort_tmp, [&](void* t, size_t& tb) {
+      return hipcub::DeviceRadixSort::SortPairsDescending(t, tb, X.qtmp.p, X.qkey.p, X.qrank.p, X.qrank2.p, c.nalive, 0, 32, st);
+    }));
   }
   hipLaunchKernelGGL(occ_init_kernel, dim3(nblk(ncells)), dim3(256), 0, st, B.pg_off, ncells, X.occ);
   // the initial run built on the device (queue_items_kernel) and read as QItems: collectPatches(queue)
@@ -4464,27 +4303,19 @@ static hipError_t expand_pass_impl(const DScene& s, FilterBuffers& B, ExpandBuff
   int ninit = 0;
   if (c.nalive) {
     static_assert(sizeof(DQItem) == sizeof(QItem), "QItem layout");
-    FCHK(grow(X.qkeep, X.cap_qkeep, na1 + 1));
-    FCHK(grow(X.qpos, X.cap_qpos, na1 + 1));
-    FCHK(grow(X.qitems, X.cap_qitems, na1 * sizeof(DQItem)));
+    FCHK(X.qkeep.grow(na1 + 1));
+    FCHK(X.qpos.grow(na1 + 1));
+    FCHK(X.qitems.grow(na1 * sizeof(DQItem)));
     hipLaunchKernelGGL(queue_keep_kernel, dim3(nblk(c.nalive)), dim3(256), 0, st, X.qrank2, B.need, c.nalive, X.qkeep);
-    size_t tb = 0;
-    FCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, X.qkeep, X.qpos, c.nalive + 1, st));
-    if (tb > X.cap_qsort) {
-      if (X.qsort_tmp) FCHK(hipFree(X.qsort_tmp));
-      X.qsort_tmp = nullptr;
-      X.cap_qsort = 0;
-      FCHK(hipMalloc(&X.qsort_tmp, tb));
-      X.cap_qsort = tb;
-    }
     FCHK(hipMemsetAsync(X.qkeep + c.nalive, 0, sizeof(int), st));
-    tb = X.cap_qsort;
-    FCHK(hipcub::DeviceScan::ExclusiveSum(X.qsort_tmp, tb, X.qkeep, X.qpos, c.nalive + 1, st));
+    FCHK(cub_run(X.qsort_tmp, [&](void* t, size_t& tb) {
+      return hipcub::DeviceScan::ExclusiveSum(t, tb, X.qkeep.p, X.qpos.p, c.nalive + 1, st);
+    }));
     hipLaunchKernelGGL(queue_items_kernel, dim3(nblk(c.nalive)), dim3(256), 0, st, X.qkey, X.qrank2, B.order, X.qkeep,
-                       X.qpos, c.nalive, reinterpret_cast<DQItem*>(X.qitems));
+                       X.qpos, c.nalive, reinterpret_cast<DQItem*>(X.qitems.p));
     FCHK(read_int(X.qpos + c.nalive, &ninit, st));
   }
-  FCHK(grow(X.counts, X.cap_cnt, (size_t)ncells));
+  FCHK(X.counts.grow((size_t)ncells));
   FCHK(memset_big(X.counts, 0, ncells, st));
   // The max-_tmp queue (P_compare; ties: earlier push first): the collected patches as a sorted
   // run, the patches pushed during the run in a heap, popped by merging the two.
@@ -4516,9 +4347,9 @@ static hipError_t expand_pass_impl(const DScene& s, FilterBuffers& B, ExpandBuff
       queue.pop_many(parents, (size_t)W);
       const int nc = (int)parents.size() - off;
       T.mark(1);
-      FCHK(grow_keep(X.parents, X.cap_par, parents.size(), (size_t)off, st));
-      FCHK(grow_keep(X.cand_coord, X.cap_coord, parents.size() * 24, (size_t)off * 24, st));
-      FCHK(grow_keep(X.cand_ok, X.cap_ok, parents.size() * 6, (size_t)off * 6, st));
+      FCHK(X.parents.grow_keep(parents.size(), (size_t)off, st));
+      FCHK(X.cand_coord.grow_keep(parents.size() * 24, (size_t)off * 24, st));
+      FCHK(X.cand_ok.grow_keep(parents.size() * 6, (size_t)off * 6, st));
       FCHK(h2d_async(X.h2d, X.parents + off, parents.data() + off, nc * sizeof(int), st));
       FCHK(hipMemsetAsync(B.counters + 3, 0, 5 * sizeof(int), st));
       // Sharded (G > 1): findEmptyBlocks of a contiguous share of the chunk's parents per rank, the
@@ -4552,8 +4383,8 @@ static hipError_t expand_pass_impl(const DScene& s, FilterBuffers& B, ExpandBuff
           return e;
         };
         if (dev) {
-          if (lerr == hipSuccess) lerr = grow(X.xsd, X.cap_xsd, std::max<size_t>(pb, 1));
-          if (lerr == hipSuccess) lerr = grow(X.xrd, X.cap_xrd, std::max<size_t>(pb * G, 1));
+          if (lerr == hipSuccess) lerr = X.xsd.grow(std::max<size_t>(pb, 1));
+          if (lerr == hipSuccess) lerr = X.xrd.grow(std::max<size_t>(pb * G, 1));
           if (lerr == hipSuccess) lerr = pack(X.xsd, hipMemcpyDeviceToDevice);
         } else {
           xsend.assign(pb, 0);
@@ -4599,21 +4430,11 @@ static hipError_t expand_pass_impl(const DScene& s, FilterBuffers& B, ExpandBuff
     stats[0] += np;
     // compact index of the free directions: the candidate / prepared-patch records are sized by
     // them, not by 6 x parents (late waves pop most of the queue, few directions are free)
-    FCHK(grow(X.cidx, X.cap_cidx, (size_t)np * 6 + 1));
+    FCHK(X.cidx.grow((size_t)np * 6 + 1));
     FCHK(hipMemsetAsync(X.cidx + (size_t)np * 6, 0, sizeof(int), st));
-    {
-      size_t tb = 0;
-      FCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, X.cand_ok, X.cidx, np * 6, st));
-      if (tb > X.cap_qsort) {
-        if (X.qsort_tmp) FCHK(hipFree(X.qsort_tmp));
-        X.qsort_tmp = nullptr;
-        X.cap_qsort = 0;
-        FCHK(hipMalloc(&X.qsort_tmp, tb));
-        X.cap_qsort = tb;
-      }
-      tb = X.cap_qsort;
-      FCHK(hipcub::DeviceScan::ExclusiveSum(X.qsort_tmp, tb, X.cand_ok, X.cidx, np * 6, st));
-    }
+    FCHK(cub_run(X.qsort_tmp, [&](void* t, size_t& tb) {
+      return hipcub::DeviceScan::ExclusiveSum(t, tb, X.cand_ok.p, X.cidx.p, np * 6, st);
+    }));
     int nok = 0;
     if (W > 1 && min_cands > 0) {
       nok = (int)ndirs;  // the chunks' free directions, already counted (count_ok_kernel): no read
@@ -4623,9 +4444,9 @@ static hipError_t expand_pass_impl(const DScene& s, FilterBuffers& B, ExpandBuff
                          {&last_idx, X.cidx + (size_t)np * 6 - 1, sizeof(int)}}));
       nok = last_idx + (last_ok != 0);
     }
-    FCHK(grow(X.cand, X.cap_cand, (size_t)std::max(nok, 1)));
-    FCHK(grow(X.prep, X.cap_prep, (size_t)std::max(nok, 1)));
-    FCHK(grow(X.status, X.cap_status, (size_t)np * 6));
+    FCHK(X.cand.grow((size_t)std::max(nok, 1)));
+    FCHK(X.prep.grow((size_t)std::max(nok, 1)));
+    FCHK(X.status.grow((size_t)np * 6));
     // wave = 1 is the reference's schedule: the parent's directions are prepared, refined and
     // committed one after the other (expand.cpp:92-101); wider waves batch every candidate.
     std::vector<int> batches{-1};
@@ -4644,25 +4465,15 @@ static hipError_t expand_pass_impl(const DScene& s, FilterBuffers& B, ExpandBuff
       FCHK(hipPeekAtLastError());
       // the survivors compacted on the device (surv_*_kernel): slots, slot2 (candidate -> survivor)
       const int nk = np * 6;
-      FCHK(grow(X.sflag, X.cap_sflag, (size_t)nk + 2));  // [nk]: 0 for the scan, [nk + 1]: prepared count
-      FCHK(grow(X.spos, X.cap_spos, (size_t)nk + 1));
-      FCHK(grow(X.slot2, X.cap_slot2, (size_t)nk));
-      FCHK(grow(X.slots, X.cap_slots, (size_t)nk));
+      FCHK(X.sflag.grow((size_t)nk + 2));  // [nk]: 0 for the scan, [nk + 1]: prepared count
+      FCHK(X.spos.grow((size_t)nk + 1));
+      FCHK(X.slot2.grow((size_t)nk));
+      FCHK(X.slots.grow((size_t)nk));
       FCHK(hipMemsetAsync(X.sflag + nk, 0, 2 * sizeof(int), st));
       hipLaunchKernelGGL(surv_flags_kernel, dim3(nblk(nk)), dim3(256), 0, st, X.status, nk, X.sflag, X.sflag + nk + 1);
-      {
-        size_t tb = 0;
-        FCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, X.sflag, X.spos, nk + 1, st));
-        if (tb > X.cap_qsort) {
-          if (X.qsort_tmp) FCHK(hipFree(X.qsort_tmp));
-          X.qsort_tmp = nullptr;
-          X.cap_qsort = 0;
-          FCHK(hipMalloc(&X.qsort_tmp, tb));
-          X.cap_qsort = tb;
-        }
-        tb = X.cap_qsort;
-        FCHK(hipcub::DeviceScan::ExclusiveSum(X.qsort_tmp, tb, X.sflag, X.spos, nk + 1, st));
-      }
+      FCHK(cub_run(X.qsort_tmp, [&](void* t, size_t& tb) {
+        return hipcub::DeviceScan::ExclusiveSum(t, tb, X.sflag.p, X.spos.p, nk + 1, st);
+      }));
       hipLaunchKernelGGL(surv_scatter_kernel, dim3(nblk(nk)), dim3(256), 0, st, X.sflag, X.spos, nk, X.slots, X.slot2);
       int sv[2] = {0, 0};
       FCHK(d2h_sync(st, {{&sv[0], X.spos + nk, sizeof(int)}, {&sv[1], X.sflag + nk + 1, sizeof(int)}}));
@@ -4675,11 +4486,11 @@ static hipError_t expand_pass_impl(const DScene& s, FilterBuffers& B, ExpandBuff
       int ovf = 0;
       auto local = [&]() -> hipError_t {
         if (m > 0) {
-          FCHK(grow(X.cand2, X.cap_cand2, (size_t)m));
-          FCHK(grow(X.prep2, X.cap_prep2, (size_t)m));
-          FCHK(grow(X.res, X.cap_res, (size_t)m));
-          FCHK(grow(X.outp, X.cap_outp, (size_t)m));
-          FCHK(grow(X.ostatus, X.cap_ost, (size_t)m));
+          FCHK(X.cand2.grow((size_t)m));
+          FCHK(X.prep2.grow((size_t)m));
+          FCHK(X.res.grow((size_t)m));
+          FCHK(X.outp.grow((size_t)m));
+          FCHK(X.ostatus.grow((size_t)m));
           hipLaunchKernelGGL(gather_slots_kernel, dim3(nblk(m)), dim3(256), 0, st, X.slots, m, X.cand, X.prep, X.cand2, X.prep2,
                              X.cidx);
           if (mine > 0) {
@@ -4707,8 +4518,8 @@ static hipError_t expand_pass_impl(const DScene& s, FilterBuffers& B, ExpandBuff
         const size_t bytes = (size_t)chunk * (sizeof(int) + sizeof(pmvs_patch));
         const bool dev = (bool)sh.exchange_dev;  // RCCL: device to device on this stream
         if (dev) {
-          if (lerr == hipSuccess) lerr = grow(X.xsd, X.cap_xsd, std::max<size_t>(bytes, 1));
-          if (lerr == hipSuccess) lerr = grow(X.xrd, X.cap_xrd, std::max<size_t>(bytes * G, 1));
+          if (lerr == hipSuccess) lerr = X.xsd.grow(std::max<size_t>(bytes, 1));
+          if (lerr == hipSuccess) lerr = X.xrd.grow(std::max<size_t>(bytes * G, 1));
           if (lerr == hipSuccess && mine > 0) {
             lerr = hipMemcpyAsync(X.xsd, X.ostatus + lo, mine * sizeof(int), hipMemcpyDeviceToDevice, st);
             if (lerr == hipSuccess)
@@ -4753,7 +4564,7 @@ static hipError_t expand_pass_impl(const DScene& s, FilterBuffers& B, ExpandBuff
       FCHK(lerr);
       if (ovf) { trace_error(kCapacityOverflow, __LINE__); return kCapacityOverflow; }  // more than NB_CAP neighbours (reported by the API)
       if (m > 0) {
-        FCHK(grow(X.crec, X.cap_crec, (size_t)m * kRecInts));
+        FCHK(X.crec.grow((size_t)m * kRecInts));
         hipLaunchKernelGGL(commit_rec_kernel, dim3(nblk(m)), dim3(256), 0, st, s, B.tgoff, X.outp, X.ostatus, X.prep2, m,
                            X.crec);
       }
@@ -4772,17 +4583,24 @@ static hipError_t expand_pass_impl(const DScene& s, FilterBuffers& B, ExpandBuff
       T.mark(7);
       if (added > 0) {
         pool_need = X.pool_host + (size_t)co.entries;
-        FCHK(grow_keep(X.d_ent, X.cap_ent, pool_need, X.pool_host, st));
+        FCHK(X.d_ent.grow_keep(pool_need, X.pool_host, st));
         set_delta();
         if ((size_t)(first + added) > pcap) {  // per-patch arrays the waves write, grown keeping their contents
           // 1.5x: the old and the new model coexist during the copy (at C5 scale ~50 M records of 1608 B)
           const size_t ncap = std::min<size_t>((size_t)cap, std::max((size_t)(first + added), pcap + pcap / 2));
-          size_t c1 = pcap, c2 = pcap, c3 = pcap, c4 = pcap;
           FCHK(grow_keep(dP, dP_cap, ncap, (size_t)first, st));
-          FCHK(grow_keep(B.preg, c1, ncap, (size_t)first, st));
-          FCHK(grow_keep(B.vreg, c2, ncap, (size_t)first, st));
-          FCHK(grow_keep(B.order, c3, ncap, (size_t)rank_next, st));
-          FCHK(grow_keep(B.hot, c4, ncap, (size_t)first, st));
+          // these four grow from the capacity the waves use (pcap <= what reserve() allocated), not from
+          // their allocation's: the free-function form with that capacity, the result stored
+          auto keep = [&](auto& b, size_t used) -> hipError_t {
+            size_t c = pcap;
+            FCHK(grow_keep(b.p, c, ncap, used, st));
+            b.cap = c;
+            return hipSuccess;
+          };
+          FCHK(keep(B.preg, (size_t)first));
+          FCHK(keep(B.vreg, (size_t)first));
+          FCHK(keep(B.order, (size_t)rank_next));
+          FCHK(keep(B.hot, (size_t)first));
           B.cap_n = 0;  // the other per-patch buffers are re-reserved by the next pass
           pcap = ncap;
           c.P = dP;
@@ -4808,7 +4626,7 @@ static hipError_t expand_pass_impl(const DScene& s, FilterBuffers& B, ExpandBuff
     }
     if (W == 1 && pbits) {
       const int2 u = make_int2(parents[0], pbits);
-      FCHK(grow(X.dupd, X.cap_dupd, 1));
+      FCHK(X.dupd.grow(1));
       FCHK(hipMemcpyAsync(X.dupd, &u, sizeof(int2), hipMemcpyHostToDevice, st));
       hipLaunchKernelGGL(dflag_kernel, dim3(1), dim3(64), 0, st, dP, X.dupd, 1);
       FCHK(hipStreamSynchronize(st));
@@ -4858,25 +4676,17 @@ __global__ __launch_bounds__(64) void lls_selftest_kernel(const float* __restric
 }
 
 hipError_t lls_selftest(const float* A, const float* b, const int* off, int nsys, int total, float* x) {
-  float *dA = nullptr, *db = nullptr, *dx = nullptr;
-  int* doff = nullptr;
-  double* scr = nullptr;
-  hipError_t e = hipMalloc((void**)&dA, (size_t)total * 5 * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&db, (size_t)total * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&dx, (size_t)nsys * 5 * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&doff, (size_t)(nsys + 1) * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc((void**)&scr, (size_t)total * 6 * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(dA, A, (size_t)total * 5 * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(db, b, (size_t)total * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(doff, off, (size_t)(nsys + 1) * sizeof(int), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(lls_selftest_kernel, dim3(nsys), dim3(64), 0, nullptr, dA, db, doff, nsys, scr, dx);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(x, dx, (size_t)nsys * 5 * sizeof(float), hipMemcpyDeviceToHost);
-  for (void* p : {(void*)dA, (void*)db, (void*)dx, (void*)doff, (void*)scr})
-    if (p) (void)hipFree(p);
-  return e;
+  DevBuf<float> dA, db, dx;
+  DevBuf<int> doff;
+  DevBuf<double> scr;
+  FCHK(dA.alloc((size_t)total * 5)); FCHK(db.alloc((size_t)total)); FCHK(dx.alloc((size_t)nsys * 5));
+  FCHK(doff.alloc((size_t)nsys + 1)); FCHK(scr.alloc((size_t)total * 6));
+  FCHK(hipMemcpy(dA, A, (size_t)total * 5 * sizeof(float), hipMemcpyHostToDevice));
+  FCHK(hipMemcpy(db, b, (size_t)total * sizeof(float), hipMemcpyHostToDevice));
+  FCHK(hipMemcpy(doff, off, (size_t)(nsys + 1) * sizeof(int), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(lls_selftest_kernel, dim3(nsys), dim3(64), 0, nullptr, dA.p, db.p, doff.p, nsys, scr.p, dx.p);
+  FCHK(hipGetLastError());
+  return hipMemcpy(x, dx, (size_t)nsys * 5 * sizeof(float), hipMemcpyDeviceToHost);
 }
 
 // ============================================================================ loop helpers
@@ -4903,8 +4713,7 @@ hipError_t compact_model(FilterBuffers& B, const pmvs_patch* src, int n, const i
   FCHK(B.reserve(n, B.cap_cells, 0, B.cap_grid));
   FCHK(hipMemcpyAsync(B.cnt, keep, n * sizeof(int), hipMemcpyDeviceToDevice, st));
   FCHK(hipMemsetAsync(B.cnt + n, 0, sizeof(int), st));
-  size_t tb = B.temp_bytes;
-  FCHK(hipcub::DeviceScan::ExclusiveSum(B.temp, tb, B.cnt, B.off, n + 1, st));
+  FCHK(cub_run(B.temp, [&](void* t, size_t& tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, B.cnt.p, B.off.p, n + 1, st); }));
   FCHK(read_int(B.off + n, nkept, st));
   pmvs_patch* dst = nullptr;
   FCHK(dst_for(*nkept, &dst));  // the target is sized by the kept records, not by the source's capacity
@@ -4991,24 +4800,8 @@ __global__ void boundary_insert_kernel(DScene s, const BRec* __restrict__ in, in
   ok[j] = (nt > 0) ? 1 : 0;  // registered in none of this scene's cells: nothing to insert
 }
 
-ClusterBuffers::~ClusterBuffers() {
-  void* ps[] = {send, recv, ins, flags, pos, cnts, temp};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-}
-
 static hipError_t scan_count(ClusterBuffers& CB, const int* f, int* pos, int n, int* total, hipStream_t st) {
-  size_t tb = 0;
-  FCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, f, pos, n + 1, st));
-  if (tb > CB.temp_bytes) {
-    if (CB.temp) (void)hipFree(CB.temp);
-    CB.temp = nullptr;
-    CB.temp_bytes = 0;
-    FCHK(hipMalloc(&CB.temp, tb));
-    CB.temp_bytes = tb;
-  }
-  tb = CB.temp_bytes;
-  FCHK(hipcub::DeviceScan::ExclusiveSum(CB.temp, tb, f, pos, n + 1, st));
+  FCHK(cub_run(CB.temp, [&](void* t, size_t& tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, f, pos, n + 1, st); }));
   return read_int(pos + n, total, st);
 }
 
@@ -5030,14 +4823,14 @@ hipError_t cluster_exchange(const DScene& s, ClusterBuffers& CB, const ClusterMa
   const int G = sh.world, me = sh.rank;
   // ---- this rank's boundary patches
   int m = 0;
-  hipError_t le = grow(CB.flags, CB.cap_flags, (size_t)n + 1);
-  if (le == hipSuccess) le = grow(CB.pos, CB.cap_pos, (size_t)n + 1);
+  hipError_t le = CB.flags.grow((size_t)n + 1);
+  if (le == hipSuccess) le = CB.pos.grow((size_t)n + 1);
   if (le == hipSuccess && n > 0) {
     hipLaunchKernelGGL(boundary_flags_kernel, dim3(nblk(n)), dim3(256), 0, st, s, src, n, cm.shared_t, CB.flags);
     le = hipMemsetAsync(CB.flags + n, 0, sizeof(int), st);
     if (le == hipSuccess) le = scan_count(CB, CB.flags, CB.pos, n, &m, st);
   }
-  if (le == hipSuccess) le = grow(CB.send, CB.cap_send, (size_t)std::max(m, 1));
+  if (le == hipSuccess) le = CB.send.grow((size_t)std::max(m, 1));
   if (le == hipSuccess && m > 0) {
     hipLaunchKernelGGL(boundary_pack_kernel, dim3(nblk(n)), dim3(256), 0, st, src, n, CB.flags, CB.pos, cm.ids, CB.send);
     le = hipGetLastError();
@@ -5062,9 +4855,9 @@ hipError_t cluster_exchange(const DScene& s, ClusterBuffers& CB, const ClusterMa
   // ---- records: fixed-size blocks of M per rank (device to device over RCCL when available)
   const size_t bytes = (size_t)M * sizeof(BRec);
   agreed = false;  // a local failure from here on is announced by the caller (loop header)
-  FCHK(grow(CB.recv, CB.cap_recv, (size_t)M * G));
+  FCHK(CB.recv.grow((size_t)M * G));
   if (sh.exchange_dev) {
-    FCHK(grow_keep(CB.send, CB.cap_send, (size_t)M, (size_t)m, st));  // pad to M records (contents past m unused)
+    FCHK(CB.send.grow_keep((size_t)M, (size_t)m, st));  // pad to M records (contents past m unused)
     if (sh.exchange_dev(CB.send, bytes, CB.recv, st) != 0) return hipErrorUnknown;
   } else {
     std::vector<char> hs(bytes, 0), hr(bytes * G);
@@ -5075,15 +4868,10 @@ hipError_t cluster_exchange(const DScene& s, ClusterBuffers& CB, const ClusterMa
   }
   // ---- insertion (readPatches semantics), compacted in rank / record order after the model
   const size_t slots = (size_t)M * G;
-  FCHK(grow(CB.ins, CB.cap_ins, slots));
-  FCHK(grow(CB.flags, CB.cap_flags, slots + 1));
-  FCHK(grow(CB.pos, CB.cap_pos, slots + 1));
-  if (CB.cap_cnts < G) {
-    if (CB.cnts) (void)hipFree(CB.cnts);
-    CB.cnts = nullptr;
-    FCHK(hipMalloc((void**)&CB.cnts, G * sizeof(int)));
-    CB.cap_cnts = G;
-  }
+  FCHK(CB.ins.grow(slots));
+  FCHK(CB.flags.grow(slots + 1));
+  FCHK(CB.pos.grow(slots + 1));
+  FCHK(CB.cnts.grow((size_t)G));
   FCHK(hipMemcpyAsync(CB.cnts, cnts.data(), G * sizeof(int), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(boundary_insert_kernel, dim3(nblk((long long)slots)), dim3(256), 0, st, s, CB.recv, G, M, me, CB.cnts,
                      cm.id2idx, cm.maxid, CB.ins, CB.flags);

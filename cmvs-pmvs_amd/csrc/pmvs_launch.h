@@ -2,7 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "pmvs_device.h"
+#include "pmvs_devbuf.h"
 #include <functional>
+#include <memory>
+#include <utility>
 #include <vector>
 
 namespace pmvsdev {
@@ -124,6 +127,16 @@ hipError_t depth_map_pass(const DScene& s, const pmvs_patch* P, int n, const int
 struct PinnedBuf {
   void* p = nullptr;
   size_t cap = 0;
+  PinnedBuf() = default;
+  PinnedBuf(PinnedBuf&& o) noexcept : p(o.p), cap(o.cap) {
+    o.p = nullptr;
+    o.cap = 0;
+  }
+  PinnedBuf& operator=(PinnedBuf&& o) noexcept {  // o leaves with the old buffer and frees it
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+    return *this;
+  }
   hipError_t ensure(size_t bytes) {
     if (bytes <= cap && p) return hipSuccess;
     if (p) (void)hipHostFree(p);
@@ -149,48 +162,44 @@ struct alignas(64) PHot {
   float normal[4];
   float dscale, ncc, unit0, pad[5];
 };
+// Buffers sized by reserve() share the logical capacities cap_n / cap_cells / cap_grid / cap_e; the
+// others grow on demand and their DevBuf holds their capacity.
 struct FilterBuffers {
   PinnedBuf pin;  // host staging of the small-groups BFS inputs
-  Reg *preg = nullptr, *vreg = nullptr, *safe = nullptr;  // per patch: registered / filterExact-safe list entries
-  unsigned long long *keys = nullptr, *keys2 = nullptr, *dpkey = nullptr;
-  long long* tgoff = nullptr;
-  int *cnt = nullptr, *off = nullptr, *cellcnt = nullptr, *pg_off = nullptr, *pg_items = nullptr, *vp_off = nullptr,
-      *vp_items = nullptr, *order = nullptr, *rank = nullptr, *flags = nullptr, *need = nullptr, *list = nullptr,
-      *counters = nullptr, *edge_off = nullptr, *edges = nullptr;
-  PHot* hot = nullptr;
-  double* scratch = nullptr;
-  void* temp = nullptr;
-  size_t temp_bytes = 0, edges_cap = 0;
-  unsigned* rbits = nullptr;  // sharded filterNeighbor: packed reject flags
-  float4* coordc = nullptr;   // collected patches' coordinates in collect order (depth maps)
-  size_t cap_rbits = 0;
+  DevBuf<Reg> preg, vreg, safe;  // per patch: registered / filterExact-safe list entries
+  DevBuf<unsigned long long> keys, keys2, dpkey;
+  DevBuf<long long> tgoff;
+  DevBuf<int> cnt, off, cellcnt, pg_off, pg_items, vp_off, vp_items, order, rank, flags, need, list, counters, edge_off,
+      edges;
+  DevBuf<PHot> hot;
+  DevBuf<double> scratch;
+  DevBuf<char> temp;        // hipcub temp storage, sized by reserve / ensure_entries for every sort and scan here
+  DevBuf<unsigned> rbits;   // sharded filterNeighbor: packed reject flags
+  DevBuf<float4> coordc;    // collected patches' coordinates in collect order (depth maps)
   // setVImagesVGrids' visibility rows (target-major bits), the collected patches' normals and used
   // targets; owner-partitioned pass (world > 1): setRefImage outcomes and the all-gathered payloads
-  unsigned long long *vrows = nullptr, *used = nullptr;
-  float4* normalc = nullptr;
-  int* refpos = nullptr;
-  char* xr = nullptr;
-  size_t cap_vrows = 0, cap_used = 0, cap_normalc = 0, cap_refpos = 0, cap_xr = 0;
+  DevBuf<unsigned long long> vrows, used;
+  DevBuf<float4> normalc;
+  DevBuf<int> refpos;
+  DevBuf<char> xr;
   // filterNeighbor's deferred quadric fits (pmvs_filter.hip QuadJobs)
-  float* qf = nullptr;
-  double* qrows = nullptr;
-  int4* qjobs = nullptr;
-  unsigned long long* qctr = nullptr;  // [0] rows used, [1] low 32 bits: jobs, [2] low 32 bits: quad_split_kernel's kb
-  unsigned long long *qkeys = nullptr, *qkeys2 = nullptr;  // jobs by descending row count
-  int *qcrows = nullptr, *qoff = nullptr;                  // per 64-job chunk: pool rows, offsets
-  size_t cap_qrows = 0;
+  DevBuf<float> qf;
+  DevBuf<double> qrows;
+  DevBuf<int4> qjobs;
+  DevBuf<unsigned long long> qctr;  // [0] rows used, [1] low 32 bits: jobs, [2] low 32 bits: quad_split_kernel's kb
+  DevBuf<unsigned long long> qkeys, qkeys2;  // jobs by descending row count
+  DevBuf<int> qcrows, qoff;                  // per 64-job chunk: pool rows, offsets
+  size_t cap_qrows = 0;  // rows of qf (qrows holds 64 x NB_CAP more)
   // the neighbour walks' NB_CAP_BIG re-walks (pmvs_filter.hip NbOverflow): overflowed work items
   // and the big form's global scratch
-  int* ovf_items = nullptr;
-  double* scratch_big = nullptr;
-  size_t cap_ovf = 0;
+  DevBuf<int> ovf_items;
+  DevBuf<double> scratch_big;
   int cap_n = 0, cap_grid = 0;
   long long cap_cells = 0;
-  size_t cap_e = 0, cap_pi = 0, cap_vi = 0;  // entries of keys/keys2, pg_items, vp_items: grown to the lists' size
+  size_t cap_e = 0;  // entries keys / keys2 are sized for (pg_items, vp_items: grown to their lists' size)
   hipError_t reserve(int n, long long ncells, int tnum, int grid);
   hipError_t ensure_entries(size_t e, int vis);
-  void release();  // frees every buffer; the next pass reserves again (PMVS_LOOP_LEAN)
-  ~FilterBuffers();
+  void release() { *this = FilterBuffers(); }  // frees every buffer; the next pass reserves again (PMVS_LOOP_LEAN)
 };
 
 // setRefImage + setGrids for the patches list[0, m) (filterExact); with refpos, only the entries whose
@@ -203,12 +212,23 @@ hipError_t launch_apply_refpos(const DScene& s, pmvs_patch* P, const int* list, 
 // ---- expansion run (pmvs_filter.hip)
 constexpr int kMaxWave = 65536;  // parents per expansion wave (device slot arrays are sized by it)
 struct CommitWork;  // device commit scratch (pmvs_filter.hip)
+struct CommitWorkDelete {
+  void operator()(CommitWork* w) const;
+};
 // Pinned staging of the per-wave host -> device index lists, with the event of its last copy
 // (recorded on the scene's stream; owned by the scene, so never waited on after that stream is gone)
 struct H2DStage {
   PinnedBuf pin;
   hipEvent_t done = nullptr;
   bool pending = false;
+  H2DStage() = default;
+  H2DStage(H2DStage&& o) noexcept : pin(std::move(o.pin)), done(o.done), pending(o.pending) { o.done = nullptr; }
+  H2DStage& operator=(H2DStage&& o) noexcept {  // o leaves with the old buffer and event and frees them
+    pin = std::move(o.pin);
+    std::swap(done, o.done);
+    std::swap(pending, o.pending);
+    return *this;
+  }
   ~H2DStage() {
     if (done) (void)hipEventDestroy(done);
   }
@@ -218,51 +238,39 @@ struct H2DStage {
 // that failed (hipErrorOutOfMemory: PMVS_ENOMEM).
 constexpr hipError_t kCapacityOverflow = hipErrorNotSupported;
 
+// Every buffer grows on demand to what a wave needs (exactly; the three the chunks of a wave append
+// to, parents / cand_coord / cand_ok, and the entry pool d_ent keep their contents).
 struct ExpandBuffers {
-  CommitWork* cm = nullptr;
+  std::unique_ptr<CommitWork, CommitWorkDelete> cm;
   long long ncells = 0;  // target cells of the pass (the commit sorts only the cell bits of its keys)
   // (the initial queue run is built on the device: qkeep / qpos / qitems)
   H2DStage h2d;
-  unsigned char* occ = nullptr;  // per target cell: pgrids holds a patch (device commit)
-  size_t cap_occ = 0;
-  int *parents = nullptr, *cand_ok = nullptr, *status = nullptr, *slots = nullptr, *ostatus = nullptr, *alive = nullptr;
-  float* cand_coord = nullptr;
-  pmvs_candidate *cand = nullptr, *cand2 = nullptr;
-  pmvs_patch *prep = nullptr, *prep2 = nullptr, *outp = nullptr;
-  pmvs_refined* res = nullptr;
-  unsigned char* counts = nullptr;
+  DevBuf<unsigned char> occ;  // per target cell: pgrids holds a patch (device commit)
+  DevBuf<int> parents, cand_ok, status, slots, ostatus, alive;
+  DevBuf<float> cand_coord;
+  DevBuf<pmvs_candidate> cand, cand2;
+  DevBuf<pmvs_patch> prep, prep2, outp;
+  DevBuf<pmvs_refined> res;
+  DevBuf<unsigned char> counts;
   // registrations committed during the run: per-cell chain heads + entry pool (FilterDev delta)
   // d_ent: the pool, {item, next} per entry (one 8-B load per chain step; round 6, separate item / next
   // arrays made every step touch two cache lines)
-  int *pg_head = nullptr, *vp_head = nullptr, *pool_used = nullptr;
-  int2* d_ent = nullptr;
-  int* tcells = nullptr;        // cells whose counts a commit changed, and their values
-  unsigned short* cellinit = nullptr;  // per-cell {count, occupied} staged for the host mirror
-  float* qtmp = nullptr;        // _tmp of the collected patches (queue)
-  float* qkey = nullptr;        // the initial queue sorted on the device: keys, collect ranks, temp
-  int *qrank = nullptr, *qrank2 = nullptr;
-  int *qkeep = nullptr, *qpos = nullptr;  // the initial run built on the device (queue_items_kernel)
-  int *sflag = nullptr, *spos = nullptr, *slot2 = nullptr;  // survivor compaction (surv_*_kernel)
-  size_t cap_sflag = 0, cap_spos = 0, cap_slot2 = 0;
-  char* qitems = nullptr;
-  size_t cap_qkeep = 0, cap_qpos = 0, cap_qitems = 0;
-  void* qsort_tmp = nullptr;
-  size_t cap_qkey = 0, cap_qrank = 0, cap_qrank2 = 0, cap_qsort = 0;
-  char *xsd = nullptr, *xrd = nullptr;  // device payload of the sharded exchange (send, all ranks)
-  size_t cap_xsd = 0, cap_xrd = 0;
-  int* cidx = nullptr;  // wave slot -> compact index of its free direction (candidate / prep records)
-  size_t cap_cidx = 0;
-  int *crec = nullptr, *acc = nullptr;  // commit records; committed record indexes
-  int2* dupd = nullptr;         // (parent, failed-direction bits) of a wave
-  unsigned char* tvals = nullptr;
+  DevBuf<int> pg_head, vp_head;
+  DevBuf<int2> d_ent;
+  DevBuf<float> qtmp;         // _tmp of the collected patches (queue)
+  DevBuf<float> qkey;         // the initial queue sorted on the device: keys, collect ranks, temp
+  DevBuf<int> qrank, qrank2;
+  DevBuf<int> qkeep, qpos;    // the initial run built on the device (queue_items_kernel)
+  DevBuf<int> sflag, spos, slot2;  // survivor compaction (surv_*_kernel)
+  DevBuf<char> qitems;
+  DevBuf<char> qsort_tmp;     // hipcub temp storage of the expansion's sorts and scans
+  DevBuf<char> xsd, xrd;      // device payload of the sharded exchange (send, all ranks)
+  DevBuf<int> cidx;           // wave slot -> compact index of its free direction (candidate / prep records)
+  DevBuf<int> crec, acc;      // commit records; committed record indexes
+  DevBuf<int2> dupd;          // (parent, failed-direction bits) of a wave
   size_t pool_host = 0;
-  size_t cap_coord = 0, cap_ok = 0, cap_cand = 0, cap_prep = 0, cap_slots = 0, cap_prep2 = 0, cap_res = 0, cap_outp = 0,
-         cap_ost = 0, cap_par = 0, cap_status = 0, cap_cand2 = 0, cap_alive = 0, cap_cnt = 0, cap_pghead = 0,
-         cap_vphead = 0, cap_ent = 0, cap_pused = 0, cap_tcells = 0, cap_tvals = 0,
-         cap_qtmp = 0, cap_crec = 0, cap_acc = 0, cap_dupd = 0, cap_cellinit = 0;
   std::vector<int> gw, gh;  // grid sizes of the target images
-  void release();  // frees every buffer; the next pass grows them again (PMVS_LOOP_LEAN)
-  ~ExpandBuffers();
+  void release() { *this = ExpandBuffers(); }  // frees every buffer; the next pass grows them again (PMVS_LOOP_LEAN)
 };
 using RefineFn = std::function<hipError_t(const pmvs_candidate* d_in, int n, pmvs_refined* d_out)>;
 // All-gather of `bytes` per rank into recv (world * bytes, rank order); 0 = OK.
@@ -301,13 +309,10 @@ struct ClusterMaps {              // device tables of one cluster scene
   int maxid;
 };
 struct ClusterBuffers {
-  BRec *send = nullptr, *recv = nullptr;
-  pmvs_patch* ins = nullptr;
-  int *flags = nullptr, *pos = nullptr, *cnts = nullptr;
-  void* temp = nullptr;
-  size_t cap_send = 0, cap_recv = 0, cap_ins = 0, cap_flags = 0, cap_pos = 0, temp_bytes = 0;
-  int cap_cnts = 0;
-  ~ClusterBuffers();
+  DevBuf<BRec> send, recv;
+  DevBuf<pmvs_patch> ins;
+  DevBuf<int> flags, pos, cnts;
+  DevBuf<char> temp;  // hipcub temp storage
 };
 // The model without other clusters' boundary patches (fix != PMVS_FIX_FOREIGN), compacted into dst.
 hipError_t drop_foreign(FilterBuffers& B, const pmvs_patch* src, int n, const CompactDst& dst_for, int* n_out,

@@ -1,4 +1,4 @@
-"""Uninitialised-memory hunt (pmvs_api.cpp / pmvs_filter.hip poison_alloc): with
+"""Uninitialised-memory hunt (pmvs_devbuf.h poison_alloc, every DevBuf allocation): with
 PMVS_POISON_ALLOC=<byte> every new device allocation of the scene is filled with that byte, so a
 kernel that reads memory no kernel wrote changes the result.  The loop (expand -> refine -> filter,
 pmvs_run_loop) and a refine batch must give byte-identical output with two different poison bytes
