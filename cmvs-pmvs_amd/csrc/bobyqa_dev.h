@@ -108,42 +108,60 @@ BQ_HD void bq_set(double (&a)[N], int i, double v) {
   for (int k = 0; k < N; ++k) a[k] = (i == k) ? v : a[k];
 }
 
-struct BqState {
-  // Powell's 1-based arrays stored without their unused row/column 0 (2216 -> 1736 bytes: the
-  // state of a chain lives in LDS); bq_begin / bq_step_impl address them through 1-based aliases
-  // (BQ_ALIASES).
+// The state is held in two parts.  BqHot is what the trust-region iteration touches between two of
+// its CALFUN returns (TRSBOX / ALTMOV / UPDATE and the main loop): it is what a chain keeps in LDS.
+// BqCold is what only PRELIM, RESCUE and the exits touch -- a handful of accesses per chain -- so its
+// latency does not matter and it may live anywhere: the split-form refine kernel keeps it in global
+// memory, which is what lets a CU hold 96 chains instead of 84.  BqState is the two side by side for
+// the users that keep one object per chain.
+struct BqHot {
+  // Powell's 1-based arrays stored without their unused row/column 0 (the state of a chain lives in
+  // LDS); bq_begin / bq_step_impl address them through 1-based aliases (BQ_ALIASES).
   // problem (rescaled space)
   double x_[BQN], xl_[BQN], xu_[BQN], s[BQN];
-  double rhobeg, rhoend;
+  double rhoend;
   int maxeval, nevals;
   // BOBYQB arrays
   double xbase_[BQN], xpt_[BQNPT][BQN], fval_[BQNPT], xopt_[BQN], gopt_[BQN], hq_[BQNH], pq_[BQNPT],
       bmat_[BQNDIM][BQN], zmat_[BQNPT][BQNPTM], sl_[BQN], su_[BQN], xnew_[BQN], xalt_[BQN], d_[BQN],
       vlag_[BQNDIM], w_[BQNDIM + BQNPT];
   double gnew_[BQN];  // TRSBOX's GNEW (Powell's W(1..N) after TRSBOX)
-  double ptsaux_[2][BQN], ptsid_[BQNPT];
   // BOBYQB scalars
-  double f, fbeg, fsave, xoptsq, rho, delta, diffa, diffb, diffc, dnorm, distsq, dsq, crvmin,
-      adelt, alpha, cauchy, beta, denom, fopt, vquad, diff, ratio, stepa, stepb;
+  double f, fsave, xoptsq, rho, delta, diffa, diffb, diffc, dnorm, distsq, dsq, crvmin,
+      adelt, alpha, cauchy, beta, denom, fopt, vquad, diff, ratio;
   int nf, kopt, kbase, nresc, ntrits, itest, nfsav, knew;
-  // PRELIM / RESCUE loop state kept across CALFUN
-  int nfm, nfx, kpt, rs_ip, rs_iq;
-  double rs_xp, rs_xq, rs_vq, rs_fbase;
   int rc;
   int resume;
   double xeval[BQN];  // unscaled point whose f is requested
-  double xout[BQN];   // unscaled final point
+};
+struct BqCold {
+  double rhobeg;                          // bq_begin, PRELIM and the start of the iteration
+  double fbeg, stepa, stepb;              // PRELIM
+  double ptsaux_[2][BQN], ptsid_[BQNPT];  // RESCUE
+  // PRELIM / RESCUE loop state kept across CALFUN
+  int nfm, nfx, kpt, rs_ip, rs_iq;
+  double rs_xp, rs_xq, rs_vq, rs_fbase;
+  double xout[BQN];  // unscaled final point
   double minf;
 };
+struct BqState : BqHot, BqCold {};
+// 6 x 16 chains of the split-form refine kernel fit its 160 KB of LDS up to this size (its handshake
+// tables and 142 B of kernel tables per chain beside the state: pmvs_refine_split.hip RefSplitLds)
+static_assert(sizeof(BqHot) <= 1512, "BqHot: the hot optimizer state of a chain");
+static_assert(sizeof(BqState) == sizeof(BqHot) + sizeof(BqCold), "BqState is BqHot and BqCold, nothing else");
 
-// 1-based views of a BqState's arrays (Powell's indexing; element 0 / row 0 / column 0 are never
-// touched), as the subroutines take them.
+// 1-based views of the state's arrays (Powell's indexing; element 0 / row 0 / column 0 are never
+// touched), as the subroutines take them.  The cold arrays' views take their address space from the
+// object they are in.
 #define BQ_A1(name) BQ_AS double* const name = (st).name##_ - 1
 #define BQ_A2(name, C) BQ_AS double(*const name)[C] = (BQ_AS double(*)[C])(&(st).name##_[0][0] - (C) - 1)
 #define BQ_ALIASES(st)                                                                                         \
   BQ_A1(x); BQ_A1(xl); BQ_A1(xu); BQ_A1(xbase); BQ_A1(fval); BQ_A1(xopt); BQ_A1(gopt); BQ_A1(hq); BQ_A1(pq); \
-  BQ_A1(sl); BQ_A1(su); BQ_A1(xnew); BQ_A1(xalt); BQ_A1(d); BQ_A1(vlag); BQ_A1(w); BQ_A1(gnew); BQ_A1(ptsid); \
-  BQ_A2(xpt, BQN); BQ_A2(bmat, BQN); BQ_A2(zmat, BQNPTM); BQ_A2(ptsaux, BQN)
+  BQ_A1(sl); BQ_A1(su); BQ_A1(xnew); BQ_A1(xalt); BQ_A1(d); BQ_A1(vlag); BQ_A1(w); BQ_A1(gnew);               \
+  BQ_A2(xpt, BQN); BQ_A2(bmat, BQN); BQ_A2(zmat, BQNPTM)
+#define BQ_COLD_ALIASES(cs)                        \
+  auto* const ptsid = &(cs).ptsid_[0] - 1;         \
+  auto* const ptsaux = (decltype(&(cs).ptsaux_[0]))(&(cs).ptsaux_[0][0] - BQN - 1)
 
 // ---------------------------------------------------------------- TRSBOX
 // The small state arrays TRSBOX reads are copied into registers at entry (xopt, hq, pq, sl, su; xpt
@@ -741,7 +759,10 @@ BQ_HD double bq_default_step(double x, double lb, double ub) {
 
 // Initialise: the nlopt_optimize -> bobyqa() wrapper up to the call of BOBYQB.
 // Returns 0 (then call bq_step with any f) or a negative NLopt error code.
-BQ_HD int bq_begin(BQ_AS BqState& st, const double* x0, const double* lb, const double* ub,
+// The cold part `cs` is given beside the hot one (a BqCold in any address space), or both as one
+// BqState.
+template <class CT>
+BQ_HD int bq_begin(BQ_AS BqHot& st, CT& cs, const double* x0, const double* lb, const double* ub,
                    double xtol_rel, int maxeval) {
   BQ_ALIASES(st);
   double dxs[BQN];
@@ -759,42 +780,42 @@ BQ_HD int bq_begin(BQ_AS BqState& st, const double* x0, const double* lb, const 
     xl[i + 1] = lb[i] / st.s[i];
     xu[i + 1] = ub[i] / st.s[i];
   }
-  st.rhobeg = fabs(dxs[0] / st.s[0]);
-  st.rhoend = xtol_rel * st.rhobeg;
+  cs.rhobeg = fabs(dxs[0] / st.s[0]);
+  st.rhoend = xtol_rel * cs.rhobeg;
   st.maxeval = maxeval;
   st.nevals = 0;
   st.rc = BQR_SUCCESS;
   st.resume = 0;
-  st.minf = 0;
+  cs.minf = 0;
   for (int j = 1; j <= BQN; ++j) {
     const double temp = xu[j] - xl[j];
-    if (temp < st.rhobeg + st.rhobeg) {
+    if (temp < cs.rhobeg + cs.rhobeg) {
       st.rc = BQR_INVALID_ARGS;
-      for (int i = 0; i < BQN; ++i) st.xout[i] = x0[i];
+      for (int i = 0; i < BQN; ++i) cs.xout[i] = x0[i];
       st.resume = -1;
       return BQR_INVALID_ARGS;
     }
     sl[j] = xl[j] - x[j];
     su[j] = xu[j] - x[j];
-    if (sl[j] >= -st.rhobeg) {
+    if (sl[j] >= -cs.rhobeg) {
       if (sl[j] >= 0.0) {
         x[j] = xl[j];
         sl[j] = 0.0;
         su[j] = temp;
       } else {
-        x[j] = xl[j] + st.rhobeg;
-        sl[j] = -st.rhobeg;
-        su[j] = bq_max(xu[j] - x[j], st.rhobeg);
+        x[j] = xl[j] + cs.rhobeg;
+        sl[j] = -cs.rhobeg;
+        su[j] = bq_max(xu[j] - x[j], cs.rhobeg);
       }
-    } else if (su[j] <= st.rhobeg) {
+    } else if (su[j] <= cs.rhobeg) {
       if (su[j] <= 0.0) {
         x[j] = xu[j];
         sl[j] = -temp;
         su[j] = 0.0;
       } else {
-        x[j] = xu[j] - st.rhobeg;
-        sl[j] = bq_min(xl[j] - x[j], -st.rhobeg);
-        su[j] = st.rhobeg;
+        x[j] = xu[j] - cs.rhobeg;
+        sl[j] = bq_min(xl[j] - x[j], -cs.rhobeg);
+        su[j] = cs.rhobeg;
       }
     }
   }
@@ -812,15 +833,33 @@ BQ_HD int bq_begin(BQ_AS BqState& st, const double* x0, const double* lb, const 
 
 // Advance the optimizer.  fin is the objective value requested by the previous call (ignored
 // on the first call).  Returns BQ_NEED_F with st.xeval set, or BQ_DONE with st.rc/st.xout.
-BQ_NI int bq_step_impl(BQ_AS BqState& st, double fin);
-BQ_HD int bq_step(BQ_AS BqState& st, double fin) {
+// Where the cold part of `st` is: `cp` is a pointer to it (a BqCold in any address space), or
+// BqColdInState{} when st is the BqHot of a BqState -- an empty argument, so that the out-of-line step
+// of the one-object users takes the one pointer it always took.
+struct BqColdInState {};
+BQ_HD BQ_AS BqCold& bq_cold(BQ_AS BqHot& st, BqColdInState) { return static_cast<BQ_AS BqState&>(st); }
+template <class CT>
+BQ_HD CT& bq_cold(BQ_AS BqHot&, CT* cp) { return *cp; }
+
+template <class CP>
+BQ_NI int bq_step_impl(BQ_AS BqHot& st, CP cp, double fin);
+template <class CP>
+BQ_HD int bq_step(BQ_AS BqHot& st, CP cp, double fin) {
   BQ_PT(t_all);
-  const int r = bq_step_impl(st, fin);
+  const int r = bq_step_impl(st, cp, fin);
   BQ_PA(3, t_all);
   return r;
 }
-BQ_NI int bq_step_impl(BQ_AS BqState& st, double fin) {
+// One object per chain: its two parts.
+BQ_HD int bq_begin(BQ_AS BqState& st, const double* x0, const double* lb, const double* ub, double xtol_rel, int maxeval) {
+  return bq_begin(static_cast<BQ_AS BqHot&>(st), static_cast<BQ_AS BqCold&>(st), x0, lb, ub, xtol_rel, maxeval);
+}
+BQ_HD int bq_step(BQ_AS BqState& st, double fin) { return bq_step(static_cast<BQ_AS BqHot&>(st), BqColdInState{}, fin); }
+template <class CP>
+BQ_NI int bq_step_impl(BQ_AS BqHot& st, CP cp, double fin) {
+  auto& cs = bq_cold(st, cp);
   BQ_ALIASES(st);
+  BQ_COLD_ALIASES(cs);
   const double half = 0.5, one = 1.0, ten = 10.0, tenth = 0.1, two = 2.0, zero = 0.0;
   double temp, sum, suma, sumb, bsum, dx, delsq, scaden, biglsq, hdiag, den, errbig, frhosq,
       bdtol, bdtest, curv, fracsq, sumpq, sumz, sumw, densav, pqold, gqsq, gisq, dist;
@@ -846,20 +885,20 @@ PSTART: {
     st.nf = 0;
     st.kopt = 1;
   PLOOP:
-    st.nfm = st.nf;
-    st.nfx = st.nf - BQN;
+    cs.nfm = st.nf;
+    cs.nfx = st.nf - BQN;
     ++st.nf;
-    if (st.nfm <= 2 * BQN) {
-      if (st.nfm >= 1 && st.nfm <= BQN) {
-        st.stepa = st.rhobeg;
-        if (su[st.nfm] == zero) st.stepa = -st.stepa;
-        xpt[st.nf][st.nfm] = st.stepa;
-      } else if (st.nfm > BQN) {
-        st.stepa = xpt[st.nf - BQN][st.nfx];
-        st.stepb = -st.rhobeg;
-        if (sl[st.nfx] == zero) st.stepb = bq_min(two * st.rhobeg, su[st.nfx]);
-        if (su[st.nfx] == zero) st.stepb = bq_max(-two * st.rhobeg, sl[st.nfx]);
-        xpt[st.nf][st.nfx] = st.stepb;
+    if (cs.nfm <= 2 * BQN) {
+      if (cs.nfm >= 1 && cs.nfm <= BQN) {
+        cs.stepa = cs.rhobeg;
+        if (su[cs.nfm] == zero) cs.stepa = -cs.stepa;
+        xpt[st.nf][cs.nfm] = cs.stepa;
+      } else if (cs.nfm > BQN) {
+        cs.stepa = xpt[st.nf - BQN][cs.nfx];
+        cs.stepb = -cs.rhobeg;
+        if (sl[cs.nfx] == zero) cs.stepb = bq_min(two * cs.rhobeg, su[cs.nfx]);
+        if (su[cs.nfx] == zero) cs.stepb = bq_max(-two * cs.rhobeg, sl[cs.nfx]);
+        xpt[st.nf][cs.nfx] = cs.stepb;
       }
     }
     for (int j = 1; j <= BQN; ++j) {
@@ -870,43 +909,43 @@ PSTART: {
     BQ_CALFUN(x, 1);
   }
 PRESUME: {
-    const double rhosq = st.rhobeg * st.rhobeg;
-    const int nf = st.nf, nfm = st.nfm, nfx = st.nfx;
+    const double rhosq = cs.rhobeg * cs.rhobeg;
+    const int nf = st.nf, nfm = cs.nfm, nfx = cs.nfx;
     st.f = fin;
     fval[nf] = st.f;
     if (nf == 1) {
-      st.fbeg = st.f;
+      cs.fbeg = st.f;
       st.kopt = 1;
     } else if (st.f < fval[st.kopt]) {
       st.kopt = nf;
     }
     if (nf <= 2 * BQN + 1) {
       if (nf >= 2 && nf <= BQN + 1) {
-        gopt[nfm] = (st.f - st.fbeg) / st.stepa;
+        gopt[nfm] = (st.f - cs.fbeg) / cs.stepa;
         if (BQNPT < nf + BQN) {
-          bmat[1][nfm] = -one / st.stepa;
-          bmat[nf][nfm] = one / st.stepa;
+          bmat[1][nfm] = -one / cs.stepa;
+          bmat[nf][nfm] = one / cs.stepa;
           bmat[BQNPT + nfm][nfm] = -half * rhosq;
         }
       } else if (nf >= BQN + 2) {
         ih = nfx * (nfx + 1) / 2;
-        temp = (st.f - st.fbeg) / st.stepb;
-        st.diff = st.stepb - st.stepa;
+        temp = (st.f - cs.fbeg) / cs.stepb;
+        st.diff = cs.stepb - cs.stepa;
         hq[ih] = two * (temp - gopt[nfx]) / st.diff;
-        gopt[nfx] = (gopt[nfx] * st.stepb - temp * st.stepa) / st.diff;
-        if (st.stepa * st.stepb < zero) {
+        gopt[nfx] = (gopt[nfx] * cs.stepb - temp * cs.stepa) / st.diff;
+        if (cs.stepa * cs.stepb < zero) {
           if (st.f < fval[nf - BQN]) {
             fval[nf] = fval[nf - BQN];
             fval[nf - BQN] = st.f;
             if (st.kopt == nf) st.kopt = nf - BQN;
-            xpt[nf - BQN][nfx] = st.stepb;
-            xpt[nf][nfx] = st.stepa;
+            xpt[nf - BQN][nfx] = cs.stepb;
+            xpt[nf][nfx] = cs.stepa;
           }
         }
-        bmat[1][nfx] = -(st.stepa + st.stepb) / (st.stepa * st.stepb);
+        bmat[1][nfx] = -(cs.stepa + cs.stepb) / (cs.stepa * cs.stepb);
         bmat[nf][nfx] = -half / xpt[nf - BQN][nfx];
         bmat[nf - BQN][nfx] = -bmat[1][nfx] - bmat[nf][nfx];
-        zmat[1][nfx] = sqrt(two) / (st.stepa * st.stepb);
+        zmat[1][nfx] = sqrt(two) / (cs.stepa * cs.stepb);
         zmat[nf][nfx] = sqrt(half) / rhosq;
         zmat[nf - BQN][nfx] = -zmat[1][nfx] - zmat[nf][nfx];
       }
@@ -925,7 +964,7 @@ PRESUME: {
   st.fsave = fval[1];
   if (st.rc != BQR_SUCCESS) goto L720;
   st.kbase = 1;
-  st.rho = st.rhobeg;
+  st.rho = cs.rhobeg;
   st.delta = st.rho;
   st.nresc = st.nf;
   st.ntrits = 0;
@@ -1095,7 +1134,7 @@ L190:  // ---- RESCUE
       if (fabs(ptsaux[2][j]) < half * fabs(ptsaux[1][j])) ptsaux[2][j] = half * ptsaux[1][j];
       for (int i = 1; i <= BQNDIM; ++i) bmat[i][j] = zero;
     }
-    st.rs_fbase = fval[st.kopt];
+    cs.rs_fbase = fval[st.kopt];
     ptsid[1] = sfrac;
     for (int j = 1; j <= BQN; ++j) {
       const int jp = j + 1, jpn = jp + BQN;
@@ -1217,11 +1256,11 @@ L190:  // ---- RESCUE
     goto R80;
   }
 R260:
-  st.kpt = 1;
+  cs.kpt = 1;
 R260LOOP:
-  if (st.kpt > BQNPT) goto R350;
-  if (ptsid[st.kpt] == zero) {
-    ++st.kpt;
+  if (cs.kpt > BQNPT) goto R350;
+  if (ptsid[cs.kpt] == zero) {
+    ++cs.kpt;
     goto R260LOOP;
   }
   if (st.maxeval > 0 && st.nevals >= st.maxeval) {
@@ -1229,7 +1268,7 @@ R260LOOP:
     goto R350;
   }
   {
-    const int kpt = st.kpt;
+    const int kpt = cs.kpt;
     ih = 0;
     for (int j = 1; j <= BQN; ++j) {
       w[j] = xpt[kpt][j];
@@ -1241,37 +1280,37 @@ R260LOOP:
       }
     }
     pq[kpt] = zero;
-    st.rs_ip = (int)ptsid[kpt];
-    st.rs_iq = (int)((double)BQNP * ptsid[kpt] - (double)(st.rs_ip * BQNP));
-    const int ip = st.rs_ip, iq = st.rs_iq;
+    cs.rs_ip = (int)ptsid[kpt];
+    cs.rs_iq = (int)((double)BQNP * ptsid[kpt] - (double)(cs.rs_ip * BQNP));
+    const int ip = cs.rs_ip, iq = cs.rs_iq;
     int ihp = 0, ihq;
     if (ip > 0) {
-      st.rs_xp = ptsaux[1][ip];
-      xpt[kpt][ip] = st.rs_xp;
+      cs.rs_xp = ptsaux[1][ip];
+      xpt[kpt][ip] = cs.rs_xp;
     }
     if (iq > 0) {
-      st.rs_xq = ptsaux[1][iq];
-      if (ip == 0) st.rs_xq = ptsaux[2][iq];
-      xpt[kpt][iq] = st.rs_xq;
+      cs.rs_xq = ptsaux[1][iq];
+      if (ip == 0) cs.rs_xq = ptsaux[2][iq];
+      xpt[kpt][iq] = cs.rs_xq;
     }
-    st.rs_vq = st.rs_fbase;
+    cs.rs_vq = cs.rs_fbase;
     if (ip > 0) {
       ihp = (ip + ip * ip) / 2;
-      st.rs_vq += st.rs_xp * (gopt[ip] + half * st.rs_xp * hq[ihp]);
+      cs.rs_vq += cs.rs_xp * (gopt[ip] + half * cs.rs_xp * hq[ihp]);
     }
     if (iq > 0) {
       ihq = (iq + iq * iq) / 2;
-      st.rs_vq += st.rs_xq * (gopt[iq] + half * st.rs_xq * hq[ihq]);
+      cs.rs_vq += cs.rs_xq * (gopt[iq] + half * cs.rs_xq * hq[ihq]);
       if (ip > 0) {
         const int iw = (ihp > ihq ? ihp : ihq) - (ip > iq ? ip - iq : iq - ip);
-        st.rs_vq += st.rs_xp * st.rs_xq * hq[iw];
+        cs.rs_vq += cs.rs_xp * cs.rs_xq * hq[iw];
       }
     }
     for (int k = 1; k <= BQNPT; ++k) {
       temp = zero;
-      if (ip > 0) temp += st.rs_xp * xpt[k][ip];
-      if (iq > 0) temp += st.rs_xq * xpt[k][iq];
-      st.rs_vq += half * pq[k] * temp * temp;
+      if (ip > 0) temp += cs.rs_xp * xpt[k][ip];
+      if (iq > 0) temp += cs.rs_xq * xpt[k][iq];
+      cs.rs_vq += half * pq[k] * temp * temp;
     }
     for (int i = 1; i <= BQN; ++i) {
       w[i] = bq_min(bq_max(xl[i], xbase[i] + xpt[kpt][i]), xu[i]);
@@ -1282,12 +1321,12 @@ R260LOOP:
     BQ_CALFUN(w, 3);
   }
 R260R: {
-    const int kpt = st.kpt, ip0 = st.rs_ip, iq0 = st.rs_iq;
+    const int kpt = cs.kpt, ip0 = cs.rs_ip, iq0 = cs.rs_iq;
     (void)ip0; (void)iq0;
     st.f = fin;
     fval[kpt] = st.f;
     if (st.f < fval[st.kopt]) st.kopt = kpt;
-    st.diff = st.f - st.rs_vq;
+    st.diff = st.f - cs.rs_vq;
     for (int i = 1; i <= BQN; ++i) gopt[i] += st.diff * bmat[kpt][i];
     for (int k = 1; k <= BQNPT; ++k) {
       sum = zero;
@@ -1313,7 +1352,7 @@ R260R: {
       }
     }
     ptsid[kpt] = zero;
-    ++st.kpt;
+    ++cs.kpt;
     goto R260LOOP;
   }
 R350:
@@ -1443,8 +1482,8 @@ L360R:
     st.fsave = st.f;
     st.rc = BQR_XTOL;
     if (st.fsave < fval[st.kopt]) {
-      st.minf = st.f;
-      for (int i = 0; i < BQN; ++i) st.xout[i] = x[i + 1] * st.s[i];
+      cs.minf = st.f;
+      for (int i = 0; i < BQN; ++i) cs.xout[i] = x[i + 1] * st.s[i];
       st.resume = -1;
       return BQ_DONE;
     }
@@ -1670,8 +1709,8 @@ L720:
     }
     st.f = fval[st.kopt];
   }
-  st.minf = st.f;
-  for (int i = 0; i < BQN; ++i) st.xout[i] = x[i + 1] * st.s[i];
+  cs.minf = st.f;
+  for (int i = 0; i < BQN; ++i) cs.xout[i] = x[i + 1] * st.s[i];
   st.resume = -1;
   return BQ_DONE;
 }

@@ -173,7 +173,7 @@ struct pmvs_scene {
   DevBuf<pmvs_patch> fpatches;
   DevBuf<int> fkeep;
   DevBuf<unsigned long long> digest;  // pmvs_loop_hash
-  int grid = 0, refine_grid = 0, tslots = 226014;
+  int grid = 0, refine_grid = 0, tslots = 225019;
   // batches below small_n candidates run the lane form, one candidate per wavefront with its BOBYQA
   // state over the lanes (tslots_small, pmvs_refine_lane.hip): their length is one chain's latency,
   // not the chip's throughput (the C3 loop, gpurun r06d: small launches 1029 -> 687 ms

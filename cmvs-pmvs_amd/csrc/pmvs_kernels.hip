@@ -1862,7 +1862,7 @@ static hipError_t launch_refine_ws(const DScene& s, const pmvs_candidate* d_in, 
   const int nc = tslots % 100;
   const int rg = refine_grid < (n + nc - 1) / nc ? refine_grid : (n + nc - 1) / nc;
   if (tslots >= 200000) {  // split form (pmvs_refine_split.hip)
-    if ((e = launch_refine_split(tslots, s, d_jobs, n, d_st, stream)) != hipSuccess) return e;
+    if ((e = launch_refine_split(tslots, s, d_jobs, n, d_st, stream, rh.bq_cold)) != hipSuccess) return e;
     if (refine_tail_on()) hipLaunchKernelGGL(refine_tail_kernel, dim3(1), dim3(64), 0, stream, d_st, 0);
     (void)hipEventRecord(ev[2], stream);
     hipLaunchKernelGGL((post_kernel<WS>), dim3(g), dim3(64), 0, stream, s, d_jobs, d_out, n, d_st);

@@ -30,6 +30,7 @@ struct RefineHost {
   float4* h_enc = nullptr;   // pinned
   double2* h_ang = nullptr;  // pinned
   size_t cap = 0;
+  DevBuf<unsigned char> bq_cold;  // the split-form refine kernel's cold optimizer state (launch_refine_split)
   // PMVS_EXPAND_PROFILE: the round trip's share of the device timeline (pre_kernel's end to the
   // refine kernel's start: start points down, host libm, angles up), summed over the batches
   bool prof = false;
@@ -50,7 +51,10 @@ hipError_t launch_refine(const DScene& s, const pmvs_candidate* d_in, RefineJob*
 // split-form refine kernel alone (pmvs_refine_split.hip), config 200000 + optimizer wavefronts * 1000 +
 // chains per optimizer wavefront, wsize 5 or 7
 bool refine_split_supported(int config);
-hipError_t launch_refine_split(int config, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st, hipStream_t stream);
+// `cold`: the chains' cold optimizer state (bobyqa_dev.h BqCold), grown here to one slot per chain of a
+// full grid; it carries nothing from one launch to the next
+hipError_t launch_refine_split(int config, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st, hipStream_t stream,
+                               DevBuf<unsigned char>& cold);
 // lane-form refine kernel (pmvs_refine_lane.hip): one candidate per wavefront, BOBYQA state spread over
 // the lanes; config 300000 (lanes per texture from tau), 300004, 300008
 bool refine_lane_supported(int config);

@@ -33,7 +33,8 @@ namespace pmvsdev {
 // ---------------------------------------------------------------- refinePatchBFGS, split form
 // One 512-thread workgroup per CU (8 wavefronts, 2 per SIMD), persistent, pulling candidates from
 // the launch's queue.  Its wavefronts have two roles:
-//   * G optimizer wavefronts: wavefront g steps CG chains, one lane each, their BqStates in LDS, so
+//   * G optimizer wavefronts: wavefront g steps CG chains, one lane each, the hot part of their
+//     optimizer states (BqHot) in LDS and the cold part (BqCold) in a global-memory slot per chain, so
 //     one instruction stream of the divergent f64 BOBYQA step serves up to CG chains (the wavefront
 //     form serves 6).  After a step it publishes its chains' objective requests, packed in chain
 //     order into chunks of at most 64 / LP textures, then evaluates unclaimed chunks of its own
@@ -64,7 +65,7 @@ template <int WS, int G, int CG>
 struct RefSplitLds {
   static constexpr int NCH = G * CG;
   static constexpr int SLOTS = CG * PMVS_MAX_TAU;  // a group's slots per round (<= 16 textures per request)
-  BqState bq[NCH];
+  BqHot bq[NCH];                            // the chain's hot optimizer state; its BqCold is in global memory
   float geo[NCH][16];                       // requesting chain: coord, normal, pxaxis, pyaxis
   double fv[NCH];                           // the chain's objective value, written by its evaluator
   int cand[NCH];                            // the chain's candidate (need 2 reads its weights)
@@ -304,13 +305,14 @@ __device__ __noinline__ unsigned long long split_chunk(const DScene& s, SPLIT_AS
 // (inlined into one body, the chunk's sample registers and the optimizer's call sites spilled).
 template <int WS, int G, int CG, int LP>
 __device__ __noinline__ void split_optimizer(const DScene& s, SPLIT_AS RefSplitLds<WS, G, CG>& C, RefineJob* __restrict__ jobs,
-                                             int n, int nc_active, DevStats* st) {
+                                             BqCold* __restrict__ cold, int n, int nc_active, DevStats* st) {
   constexpr int TS = WAVE / LP;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & (WAVE - 1);
   const int g = wave;
   const bool owner = lane < CG && lane < nc_active;
   const int c = g * CG + (lane < CG ? lane : 0);
-  BQ_AS BqState& bq = *(BQ_AS BqState*)&C.bq[c];
+  BQ_AS BqHot& bq = *(BQ_AS BqHot*)&C.bq[c];
+  BqCold& bc = cold[(size_t)blockIdx.x * (G * CG) + c];  // what PRELIM, RESCUE and the exits touch
   RefineSetup R;
   int cand = -1, need = 0, evals = 0, size = 0, nimg = 0, rc = 0;
   bool exhausted = !owner;
@@ -343,14 +345,14 @@ __device__ __noinline__ void split_optimizer(const DScene& s, SPLIT_AS RefSplitL
       C.cand[c] = cand;
       evals = 0;
       const double x0[3] = {J.x0[0], J.x0[1], J.x0[2]};
-      bq_begin(bq, x0, lb, ub, 1.e-7, 1000);
+      bq_begin(bq, bc, x0, lb, ub, 1.e-7, 1000);
       fv = 0.0;
       need = 0;
     }
     SP_MARK(0);
     // (b) advance BOBYQA when the chain holds an objective value (or just started)
     if (cand >= 0 && need == 0) {
-      const int r = (bq.resume < 0) ? BQ_DONE : bq_step(bq, fv);
+      const int r = (bq.resume < 0) ? BQ_DONE : bq_step(bq, &bc, fv);
       if (r == BQ_NEED_F) {
         need = 1;
         const double xe[3] = {bq.xeval[0], bq.xeval[1], bq.xeval[2]};
@@ -362,7 +364,7 @@ __device__ __noinline__ void split_optimizer(const DScene& s, SPLIT_AS RefSplitL
         J.refine_code = rc;
         J.evals = evals;
         if (success) {
-          const double xo[3] = {bq.xout[0], bq.xout[1], bq.xout[2]};
+          const double xo[3] = {bc.xout[0], bc.xout[1], bc.xout[2]};
           decode(s, R, xo, fcoord, fnormal);
           if (nimg < 2) {  // computeINCC returns 2.0 without grabbing (optim.cpp:866)
             J.ncc = (float)(1.0 - (double)unrobustincc(2.0f));
@@ -527,7 +529,7 @@ __device__ __noinline__ void split_evaluator(const DScene& s, SPLIT_AS RefSplitL
 
 template <int WS, int G, int CG, int LP>
 __global__ __launch_bounds__(SPLIT_THREADS) __attribute__((amdgpu_waves_per_eu(SPLIT_WPE))) void refine_split_kernel(
-    DScene s, RefineJob* __restrict__ jobs, int n, int nc_active, DevStats* st) {
+    DScene s, RefineJob* __restrict__ jobs, BqCold* __restrict__ cold, int n, int nc_active, DevStats* st) {
   using L = RefSplitLds<WS, G, CG>;
   static_assert(G >= 1 && G <= SPLIT_THREADS / WAVE && CG <= WAVE && CG <= 255, "roles");
   static_assert(sizeof(L) <= 160 * 1024, "LDS");
@@ -544,17 +546,18 @@ __global__ __launch_bounds__(SPLIT_THREADS) __attribute__((amdgpu_waves_per_eu(S
   }
   __syncthreads();
   if (wave < G)
-    split_optimizer<WS, G, CG, LP>(s, *(SPLIT_AS RefSplitLds<WS, G, CG>*)&C, jobs, n, nc_active, st);
+    split_optimizer<WS, G, CG, LP>(s, *(SPLIT_AS RefSplitLds<WS, G, CG>*)&C, jobs, cold, n, nc_active, st);
   else
     split_evaluator<WS, G, CG, LP>(s, *(SPLIT_AS RefSplitLds<WS, G, CG>*)&C, jobs, st);
 }
 
 
 // config = 200000 + LP * 10000 + optimizer wavefronts * 1000 + chains per optimizer wavefront, LP =
-// lanes per texture in the evaluators (0 reads as 1); WS <= 7
+// lanes per texture in the evaluators (0 reads as 1); WS <= 7.  The chains a CU holds (G * CG) are
+// bounded by LDS alone: 1512 B of BqHot and 142 B of tables per chain allow 96 (6 x 16, 5 x 19, 7 x 13).
 #if SPLIT_THREADS_ == 512
-#define PMVS_SPLIT_CONFIGS(X) X(0, 2, 32) X(0, 4, 16) X(2, 4, 16) X(2, 5, 16) X(2, 6, 12) X(2, 6, 14) X(2, 7, 12) \
-  X(2, 8, 10) X(3, 6, 14) X(4, 5, 16) X(4, 6, 14) X(4, 7, 12) X(4, 8, 10) X(8, 8, 10)
+#define PMVS_SPLIT_CONFIGS(X) X(0, 2, 32) X(0, 4, 16) X(2, 4, 16) X(2, 5, 16) X(2, 5, 19) X(2, 6, 12) X(2, 6, 14) X(2, 6, 15) \
+  X(2, 6, 16) X(2, 7, 12) X(2, 7, 13) X(2, 8, 10) X(3, 6, 14) X(4, 5, 16) X(4, 6, 14) X(4, 7, 12) X(4, 8, 10) X(8, 8, 10)
 #else
 #define PMVS_SPLIT_CONFIGS(X) X(2, 4, 20) X(4, 4, 20) X(8, 4, 20) X(2, 2, 40) X(4, 3, 24)
 #endif
@@ -569,7 +572,8 @@ bool refine_split_supported(int config) {
 }
 
 template <int WS>
-static hipError_t launch_split_ws(int config, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st, hipStream_t stream) {
+static hipError_t launch_split_ws(int config, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st, hipStream_t stream,
+                                  DevBuf<unsigned char>& cold) {
   const int gw = (config / 1000) % 10, cg = config % 1000;
   int dev = 0, cus = 0;
   hipError_t e;
@@ -581,10 +585,12 @@ static hipError_t launch_split_ws(int config, const DScene& s, RefineJob* d_jobs
   const int sgrid = cus < (n + gw - 1) / gw ? cus : (n + gw - 1) / gw;
   const int per = (n + sgrid * gw - 1) / (sgrid * gw);
   const int nca = per < cg ? per : cg;
+  // a BqCold per chain of the largest grid; never read before the chain's bq_begin wrote it
+  if ((e = cold.grow((size_t)cus * gw * cg * sizeof(BqCold))) != hipSuccess) return e;
 #define PMVS_SPLIT_LAUNCH(LPc, Gc, CGc)                                                                                   \
   case 200000 + LPc * 10000 + Gc * 1000 + CGc:                                                                             \
     hipLaunchKernelGGL((refine_split_kernel<WS, Gc, CGc, (LPc > 0 ? LPc : 1)>), dim3(sgrid), dim3(SPLIT_THREADS), 0, stream, \
-                       s, d_jobs, n, nca, d_st);                                                                           \
+                       s, d_jobs, (BqCold*)cold.p, n, nca, d_st);                                                          \
     break;
   switch (config) {
     PMVS_SPLIT_CONFIGS(PMVS_SPLIT_LAUNCH)
@@ -594,11 +600,12 @@ static hipError_t launch_split_ws(int config, const DScene& s, RefineJob* d_jobs
   return hipGetLastError();
 }
 
-hipError_t launch_refine_split(int config, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st, hipStream_t stream) {
+hipError_t launch_refine_split(int config, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st, hipStream_t stream,
+                               DevBuf<unsigned char>& cold) {
   if (n <= 0) return hipSuccess;
   switch (s.wsize) {
-    case 5: return launch_split_ws<5>(config, s, d_jobs, n, d_st, stream);
-    case 7: return launch_split_ws<7>(config, s, d_jobs, n, d_st, stream);
+    case 5: return launch_split_ws<5>(config, s, d_jobs, n, d_st, stream, cold);
+    case 7: return launch_split_ws<7>(config, s, d_jobs, n, d_st, stream, cold);
     default: return hipErrorInvalidValue;
   }
 }
