@@ -25,16 +25,12 @@
 // immediate offsets, and a register peak of the routine itself rather than of the whole inlined
 // kernel (the inlined optimizer hoisted state into ~470 VGPR+AGPR and capped the refine kernel at
 // one wavefront per SIMD).  Host builds (tests/csrc/bq_host.cpp) see plain pointers.
-// -DBQ_PRIVATE (experiment builds): the state lives in per-lane private memory (scratch) instead,
-// so a wavefront can hold 64 chains.
-#if defined(__HIP_DEVICE_COMPILE__) && defined(BQ_PRIVATE)
-#define BQ_AS __attribute__((address_space(5)))
-#elif defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
 #define BQ_AS __attribute__((address_space(3)))
 #else
 #define BQ_AS
 #endif
-#if defined(__HIPCC__) && !defined(BQ_INLINE)
+#if defined(__HIPCC__)
 #define BQ_NI __host__ __device__ inline __attribute__((noinline))
 #else
 #define BQ_NI BQ_HD
@@ -47,17 +43,7 @@
 // registers across the stores to xnew / xalt / w instead of being re-read from LDS after each of
 // them (UPDATE: 132 -> 40 LDS reads, ALTMOV: 206 -> 127, gfx950 ISA).  TRSBOX keeps plain pointers:
 // hoisting its xpt / hq / pq reads out of the Hessian-product loops overflows its 256 registers
-// (944 B of scratch per lane) -- BQ_RST is empty unless -DBQ_TRSBOX_RESTRICT.
-#if defined(BQ_NO_RESTRICT)
-#define BQ_RS
-#else
-#define BQ_RS __restrict__
-#endif
-#if defined(BQ_TRSBOX_RESTRICT)
-#define BQ_RST __restrict__
-#else
-#define BQ_RST
-#endif
+// (944 B of scratch per lane).
 
 namespace pmvsdev {
 
@@ -168,12 +154,11 @@ static_assert(sizeof(BqState) == sizeof(BqHot) + sizeof(BqCold), "BqState is BqH
 // stays in LDS: with it the routine exceeds 256 registers) and d / gnew are kept there until the
 // exit, so its loops run on registers instead of chains of dependent LDS round trips; the
 // arithmetic is unchanged.
-BQ_NI void bq_trsbox(const BQ_AS double (*BQ_RST xpt)[BQN], const BQ_AS double* BQ_RST xopt_m, const BQ_AS double* BQ_RST gopt,
-                     const BQ_AS double* BQ_RST hq_m, const BQ_AS double* BQ_RST pq_m, const BQ_AS double* BQ_RST sl_m,
-                     const BQ_AS double* BQ_RST su_m, double delta, BQ_AS double* BQ_RST xnew, BQ_AS double* BQ_RST d_m,
-                     BQ_AS double* BQ_RST gnew_m, BQ_AS double* BQ_RST dsq_out, BQ_AS double* BQ_RST crvmin_out) {
+BQ_NI void bq_trsbox(const BQ_AS double (*xpt)[BQN], const BQ_AS double* xopt_m, const BQ_AS double* gopt,
+                     const BQ_AS double* hq_m, const BQ_AS double* pq_m, const BQ_AS double* sl_m,
+                     const BQ_AS double* su_m, double delta, BQ_AS double* xnew, BQ_AS double* d_m,
+                     BQ_AS double* gnew_m, BQ_AS double* dsq_out, BQ_AS double* crvmin_out) {
   const double half = 0.5, one = 1.0, onemin = -1.0, zero = 0.0;
-#if !defined(BQ_TRSBOX_LDS)
   double xopt[BQN + 1], hq[BQNH + 1], pq[BQNPT + 1], sl[BQN + 1], su[BQN + 1], d[BQN + 1], gnew[BQN + 1];
   for (int k = 1; k <= BQNPT; ++k) pq[k] = pq_m[k];
   for (int i = 1; i <= BQNH; ++i) hq[i] = hq_m[i];
@@ -182,12 +167,6 @@ BQ_NI void bq_trsbox(const BQ_AS double (*BQ_RST xpt)[BQN], const BQ_AS double* 
     sl[i] = sl_m[i];
     su[i] = su_m[i];
   }
-#define BQ_D_AT(i) bq_get(d, i)
-#else  // (experiment builds) every array in LDS
-  const BQ_AS double *const xopt = xopt_m, *const hq = hq_m, *const pq = pq_m, *const sl = sl_m, *const su = su_m;
-  BQ_AS double *const d = d_m, *const gnew = gnew_m;
-#define BQ_D_AT(i) d[i]
-#endif
   double xbdi[BQN + 1], s[BQN + 1], hs[BQN + 1], hred[BQN + 1];
   int iterc = 0, nact = 0, itermax = 0, itcsav = 0, iact = 0, isav = 0, iu = 0;
   double delsq, qred, crvmin, beta = 0, stepsq = 0, gredsq = 0, resid, ds, shs = 0, temp, blen = 0,
@@ -276,7 +255,7 @@ L50:
     ++nact;
     bq_set(xbdi, iact, bq_get(s, iact) < zero ? onemin : one);
     {
-      const double di = BQ_D_AT(iact);
+      const double di = bq_get(d, iact);
       delsq -= di * di;
     }
     if (delsq <= zero) goto L90;
@@ -463,7 +442,7 @@ L190: {
     return;
   }
 L210: {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(BQ_TRSBOX_LDS)
+#if defined(__HIP_DEVICE_COMPILE__)
     // xpt is read here only: re-read it per product instead of letting the compiler hoist its 21
     // loads out of the iterations (with them in registers the routine spills)
     __asm__ volatile("" ::: "memory");
@@ -492,13 +471,12 @@ L210: {
   }
 }
 
-#undef BQ_D_AT
-
 // ---------------------------------------------------------------- ALTMOV
-BQ_NI void bq_altmov(const BQ_AS double (*BQ_RS xpt)[BQN], const BQ_AS double* BQ_RS xopt, const BQ_AS double (*BQ_RS bmat)[BQN],
-                     const BQ_AS double (*BQ_RS zmat)[BQNPTM], const BQ_AS double* BQ_RS sl, const BQ_AS double* BQ_RS su, int kopt,
-                     int knew, double adelt, BQ_AS double* BQ_RS xnew, BQ_AS double* BQ_RS xalt, BQ_AS double* BQ_RS alpha,
-                     BQ_AS double* BQ_RS cauchy) {
+BQ_NI void bq_altmov(const BQ_AS double (*__restrict__ xpt)[BQN], const BQ_AS double* __restrict__ xopt,
+                     const BQ_AS double (*__restrict__ bmat)[BQN], const BQ_AS double (*__restrict__ zmat)[BQNPTM],
+                     const BQ_AS double* __restrict__ sl, const BQ_AS double* __restrict__ su, int kopt, int knew,
+                     double adelt, BQ_AS double* __restrict__ xnew, BQ_AS double* __restrict__ xalt,
+                     BQ_AS double* __restrict__ alpha, BQ_AS double* __restrict__ cauchy) {
   const double half = 0.5, one = 1.0, zero = 0.0;
   const double cnst = one + sqrt(2.0);
   double glag[BQN + 1], hcol[BQNPT + 1], w[2 * BQN + 1];
@@ -701,8 +679,8 @@ L120:
 }
 
 // ---------------------------------------------------------------- UPDATE
-BQ_NI void bq_update(BQ_AS double (*BQ_RS bmat)[BQN], BQ_AS double (*BQ_RS zmat)[BQNPTM], BQ_AS double* BQ_RS vlag, double beta,
-                     double denom, int knew, BQ_AS double* BQ_RS w) {
+BQ_NI void bq_update(BQ_AS double (*__restrict__ bmat)[BQN], BQ_AS double (*__restrict__ zmat)[BQNPTM],
+                     BQ_AS double* __restrict__ vlag, double beta, double denom, int knew, BQ_AS double* __restrict__ w) {
   const double one = 1.0, zero = 0.0;
   double ztest = zero, temp, tempa, tempb, alpha, tau;
   for (int k = 1; k <= BQNPT; ++k)

@@ -173,13 +173,15 @@ struct pmvs_scene {
   DevBuf<pmvs_patch> fpatches;
   DevBuf<int> fkeep;
   DevBuf<unsigned long long> digest;  // pmvs_loop_hash
-  int grid = 0, refine_grid = 0, tslots = 225019;
+  int grid = 0, refine_grid = 0;
+  RefineLayout layout = split_layout(2, 5, 19);  // pmvs_refine_layouts.h
   // batches below small_n candidates run the lane form, one candidate per wavefront with its BOBYQA
-  // state over the lanes (tslots_small, pmvs_refine_lane.hip): their length is one chain's latency,
+  // state over the lanes (layout_small, pmvs_refine_lane.hip): their length is one chain's latency,
   // not the chip's throughput (the C3 loop, gpurun r06d: small launches 1029 -> 687 ms
-  // per step against the workgroup form 132042, split point 7000 against 5000 / 10000)
-  int tslots_small = 300000, small_n = 7000;
-  int refine_cfg(int n) const { return n < small_n ? tslots_small : tslots; }
+  // per step against the retired workgroup form, split point 7000 against 5000 / 10000)
+  RefineLayout layout_small = lane_layout(0);
+  int small_n = 7000;
+  const RefineLayout& refine_cfg(int n) const { return n < small_n ? layout_small : layout; }
   // expansion sharding (pmvs_scene_set_shard) and the kept result of pmvs_expand_run(out = NULL)
   int shard_rank = 0, shard_world = 1;
   pmvs_allgather_fn shard_fn = nullptr;
@@ -452,17 +454,14 @@ pmvs_status pmvs_scene_create(const pmvs_scene_desc* d, int32_t device, pmvs_sce
   int wpc = 8;  // 1206: 19.5 KB LDS, <= 256 registers -> 8 resident per CU
   if (const char* e = getenv("PMVS_REFINE_WAVES_PER_CU")) wpc = std::max(1, std::min(32, atoi(e)));
   if (const char* e = getenv("PMVS_REFINE_CONFIG")) {  // one layout for every batch size
-    sc->tslots = atoi(e);
-    if (!refine_config_supported(sc->tslots)) sc->tslots = 1206;
-    sc->tslots_small = sc->tslots;
+    if (!parse(atoi(e), sc->layout)) sc->layout = kWaveDefault;
+    sc->layout_small = sc->layout;
   }
   if (const char* e = getenv("PMVS_REFINE_LARGE_CONFIG")) {  // the layout of the batches >= small_n only
-    const int v = atoi(e);
-    if (refine_config_supported(v)) sc->tslots = v;
+    (void)parse(atoi(e), sc->layout);  // an unsupported number is ignored
   }
   if (const char* e = getenv("PMVS_REFINE_SMALL_CONFIG")) {  // the layout of the batches < small_n only
-    const int v = atoi(e);
-    if (refine_config_supported(v)) sc->tslots_small = v;
+    (void)parse(atoi(e), sc->layout_small);
   }
   if (const char* e = getenv("PMVS_REFINE_SMALL_N")) sc->small_n = std::max(0, atoi(e));
   sc->refine_grid = std::max(1, prop.multiProcessorCount) * wpc;
@@ -1100,8 +1099,8 @@ pmvs_status expand_device(pmvs_scene* sc, int n0, int wave, int min_cands, int c
     refined += m;
     ++launches;
     pending = true;
-    const int cfg = sc->refine_cfg(m);
-    pending_small = m < sc->small_n;  // the small batches (refine_cfg: tslots_small)
+    const RefineLayout& cfg = sc->refine_cfg(m);
+    pending_small = m < sc->small_n;  // the small batches (refine_cfg: layout_small)
     launches_small += pending_small ? 1 : 0;
     return launch_refine(sc->ds, d_in, sc->jobs.p, d_out, m, sc->stats.p, sc->grid, sc->refine_grid, cfg, sc->stream,
                          sc->kev, sc->rhost);

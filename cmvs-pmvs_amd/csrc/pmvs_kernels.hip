@@ -30,10 +30,6 @@
 
 namespace pmvsdev {
 
-#ifndef REFINE_TSLOTS
-#define REFINE_TSLOTS 48
-#endif
-
 typedef uint16_t img_t;       // an image index in LDS (a scene has at most 32767 views: pmvs_scene_create)
 
 template <int WS>
@@ -882,9 +878,7 @@ template <int WS, int TSLOTS, int NC>
 struct RefLds {
   static constexpr int S = WS * WS;
   static constexpr int SP = (S + 3) & ~3;  // channel rows padded to 16 B (float4 reads)
-#if !defined(BQ_PRIVATE)
   BqState bq[NC];                    // optimizer state of the wave's NC chains (lane c owns bq[c])
-#endif
   alignas(16) float tex[TSLOTS][3][SP];  // per texture: R, G, B rows of the S samples
   float ave[TSLOTS][4];
   long long jbase[TSLOTS];
@@ -913,8 +907,8 @@ struct RefLds {
   } while (0)
 #endif
 
-// Per-texture steps of the cooperative objective evaluation, shared by the wavefront form
-// (refine_v2_kernel) and the workgroup form (refine_wg_kernel).  L is the kernel's LDS layout
+// Per-texture steps of the wavefront form's cooperative objective evaluation (refine_v2_kernel).  L is
+// the kernel's LDS layout
 // (jreq / jidx / views / geo name the slot's request, tex / ave / j* hold the slot).
 // setup, one thread per texture: tex_geom (pmvs_refine.h) computes the frame, tex_setup stores it.
 template <int WS, class L>
@@ -1095,12 +1089,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE_WPE(N
     DScene s, RefineJob* __restrict__ jobs, int n, DevStats* st) {
   __shared__ RefLds<WS, TSLOTS, NC> C;
   const int lane = lane_id();
-#if defined(BQ_PRIVATE)
-  BqState bq_priv;
-  BQ_AS BqState& bq = *(BQ_AS BqState*)&bq_priv;
-#else
   BQ_AS BqState& bq = *(BQ_AS BqState*)&C.bq[lane < NC ? lane : 0];
-#endif
   RefineSetup R;
   int cand = -1, need = 0, evals = 0, size = 0, nimg = 0, rc = 0;
   bool exhausted = lane >= NC;  // lanes >= NC only help evaluate
@@ -1248,240 +1237,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE_WPE(N
     atomicAdd(&st->rounds, rounds);
     atomicAdd(&st->chunks, chunks);
     for (int i = 0; i < 8; ++i) atomicAdd(&st->prof[i], prof[i]);
-    atomicMax(&st->t_last, __builtin_amdgcn_s_memrealtime());
-  }
-}
-
-// ---------------------------------------------------------------- refinePatchBFGS, workgroup form
-// One 256-thread workgroup (4 wavefronts, one per SIMD) owns NC chains whose optimizer states
-// live in the workgroup's LDS.  Chain c is stepped by lane c % (NC/OW) of wavefront c / (NC/OW):
-// with OW = 1 a single wavefront advances all NC chains in one instruction stream (NC lanes per
-// f64 instruction instead of the wavefront form's 6), with OW = 4 every SIMD steps NC/4 of them.
-// The requests of a round are packed, in chain order, into chunks of <= TS texture slots, and all
-// 256 threads evaluate a chunk: thread-per-texture setup / moments / dot spread over the four
-// wavefronts (consecutive slots per wavefront: conflict-free LDS rows), thread-per-sample gather
-// and scaling.  Results, optimizer trajectories and counters equal the wavefront form's.
-constexpr int WG_THREADS = 256;
-constexpr int WG_LDS_BYTES = 160 * 1024;
-
-template <int WS, int NC, int WGPC>
-struct RefWgFit {  // texture slots (<= 64) that fit next to NC optimizer states, WGPC workgroups per CU
-  static constexpr int SP = (WS * WS + 3) & ~3;
-  static constexpr int per_slot = 3 * SP * 4 + 4 * 4 + 8 + 4 * 4 + (2 * WS + 4) * 4 + 4;
-  static constexpr int fixed = NC * ((int)sizeof(BqState) + 16 * 4 + PMVS_MAX_TAU * 2 + 4 * 4) + 4 * (NC + 1) + 64;
-  static constexpr int fit = (WG_LDS_BYTES / WGPC - fixed) / per_slot - 1;
-  static constexpr int slots = fit < 64 ? fit : 64;
-};
-
-template <int WS, int NC, int TS>
-struct RefWgLds {
-  static constexpr int S = WS * WS;
-  static constexpr int SP = (S + 3) & ~3;
-  BqState bq[NC];                          // chain c's optimizer state
-  alignas(16) float tex[TS][3][SP];       // slot: R, G, B rows of the S samples
-  float ave[TS][4];
-  long long jbase[TS];
-  int jvalid[TS], jW[TS], jreq[TS], jidx[TS];
-  float jrow[TS][WS][2], jdx[TS][2], jdy[TS][2];
-  float jres[TS];
-  float geo[NC][16];                       // requesting chain: coord, normal, pxaxis, pyaxis
-  unsigned short views[NC][PMVS_MAX_TAU];  // chain: first size images
-  int rsize[NC];                           // this round's request size (0: none)
-  int rfirst[NC], rchunk[NC];              // its first slot and chunk
-  int alive[NC];                           // chain holds a candidate or may still get one
-  int chunk_jobs[NC + 1];
-  int nchunk, live;
-};
-
-template <int WS, int NC, int TS, int OW>
-__global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(REFINE_WPE(NC)))) void refine_wg_kernel(
-    DScene s, RefineJob* __restrict__ jobs, int n, int nc_active, DevStats* st) {
-  constexpr int CPW = NC / OW;
-  static_assert(NC % OW == 0 && NC <= WAVE && OW >= 1 && OW <= WG_THREADS / WAVE, "chain layout");
-  static_assert(TS >= PMVS_MAX_TAU, "a request must fit one chunk");
-  static_assert(sizeof(RefWgLds<WS, NC, TS>) <= WG_LDS_BYTES, "LDS");
-  __shared__ RefWgLds<WS, NC, TS> C;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & (WAVE - 1);
-  // chain c = lane * OW + wave: the first nc_active chains (small batches spread over more
-  // workgroups) fall on every optimizer wavefront
-  const int cidx = lane * OW + wave;
-  const bool owner = wave < OW && lane < CPW && cidx < nc_active;
-  const int c = owner ? cidx : 0;
-  BQ_AS BqState& bq = *(BQ_AS BqState*)&C.bq[c];
-  RefineSetup R;
-  int cand = -1, need = 0, evals = 0, size = 0, nimg = 0, rc = 0;
-  bool exhausted = !owner;
-  double fv = 0.0;
-  float fcoord[4], fnormal[4];
-  unsigned long long tex_valid = 0, grabs = 0, nevals = 0, rounds = 0, chunks = 0;
-  const double lb[3] = {-HUGE_VAL, -23.99999, -23.99999};
-  const double ub[3] = {HUGE_VAL, 23.99999, 23.99999};
-  // chains beyond nc_active never publish: they read as idle and dead (the packing and the loop's
-  // exit test read every chain's entry)
-  if (tid < NC) {
-    C.rsize[tid] = 0;
-    C.alive[tid] = 0;
-  }
-  if (tid == 0) atomicMax(&st->t_first_inv, ~__builtin_amdgcn_s_memrealtime());
-  __syncthreads();
-  for (;;) {
-    bool req = false;
-    if (owner) {
-      // (a) refill an idle chain from the queue (skipping candidates that failed preProcess)
-      while (cand < 0 && !exhausted) {
-        const unsigned long long q = atomicAdd(&st->queue2, 1ull);
-        if (q >= (unsigned long long)n) {
-          exhausted = true;
-          atomicMax(&st->t_drain_inv, ~__builtin_amdgcn_s_memrealtime());
-          break;
-        }
-        const RefineJob& J = jobs[q];
-        if (J.status != PMVS_ACCEPTED) continue;
-        cand = (int)q;
-        for (int i = 0; i < 4; ++i) { R.center[i] = J.center[i]; R.ray[i] = J.ray[i]; }
-        R.dscale = J.dscale;
-        R.ascale = s.ascale;
-        R.ref = J.images[0];
-        nimg = J.nimg;
-        size = imin(s.tau, nimg);
-        for (int i = 0; i < size; ++i) C.views[c][i] = J.images[i];
-        evals = 0;
-        const double x0[3] = {J.x0[0], J.x0[1], J.x0[2]};
-        bq_begin(bq, x0, lb, ub, 1.e-7, 1000);
-        fv = 0.0;
-        need = 0;
-      }
-      // (b) advance BOBYQA when it holds an objective value (or just started)
-      if (cand >= 0 && need == 0) {
-        const int r = (bq.resume < 0) ? BQ_DONE : bq_step(bq, fv);
-        if (r == BQ_NEED_F) {
-          need = 1;
-          const double xe[3] = {bq.xeval[0], bq.xeval[1], bq.xeval[2]};
-          decode(s, R, xe, fcoord, fnormal);
-        } else {
-          rc = bq.rc;
-          const bool success = (rc == BQR_SUCCESS || rc == 2 || rc == 3 || rc == BQR_XTOL);
-          RefineJob& J = jobs[cand];
-          J.refine_code = rc;
-          J.evals = evals;
-          if (success) {
-            const double xo[3] = {bq.xout[0], bq.xout[1], bq.xout[2]};
-            decode(s, R, xo, fcoord, fnormal);
-            if (nimg < 2) {  // computeINCC returns 2.0 without grabbing (optim.cpp:866)
-              J.ncc = (float)(1.0 - (double)unrobustincc(2.0f));
-              for (int i = 0; i < 4; ++i) { J.rcoord[i] = fcoord[i]; J.rnormal[i] = fnormal[i]; }
-              cand = -1;
-            } else {
-              need = 2;  // final computeINCC (robust, weighted) at the refined geometry
-            }
-          } else {
-            cand = -1;  // geometry and _ncc stay unrefined (optim.cpp:649-655)
-          }
-        }
-      }
-      // (c) publish the request
-      req = (cand >= 0 && need != 0);
-      if (req) {
-        float px[4], py[4];
-        get_paxes(s, s.views[R.ref], fcoord, fnormal, px, py);
-        for (int i = 0; i < 4; ++i) {
-          C.geo[c][i] = fcoord[i]; C.geo[c][4 + i] = fnormal[i];
-          C.geo[c][8 + i] = px[i]; C.geo[c][12 + i] = py[i];
-        }
-      }
-      C.rsize[c] = req ? size : 0;
-      C.alive[c] = (cand >= 0 || !exhausted) ? 1 : 0;
-    }
-    __syncthreads();
-    // (d) pack the round's requests into chunks of <= TS slots, in chain order
-    if (wave == 0) {
-      const int sz = lane < NC ? C.rsize[lane] : 0;
-      bool pending = sz > 0;
-      int k = 0;
-      while (__ballot(pending) != 0ull) {
-        const int off = wave_excl_scan(pending ? sz : 0);
-        const bool in = pending && (off + sz <= TS);
-        const int nj = __shfl(off + sz, 63 - __clzll(__ballot(in)));
-        if (in) {
-          C.rfirst[lane] = off;
-          C.rchunk[lane] = k;
-        }
-        if (lane == 0) C.chunk_jobs[k] = nj;
-        pending = pending && !in;
-        ++k;
-      }
-      const bool al = lane < NC && C.alive[lane] != 0;
-      if (lane == 0) {
-        C.nchunk = k;
-        C.live = __ballot(al) != 0ull ? 1 : 0;
-      }
-    }
-    __syncthreads();
-    const int nchunk = C.nchunk;
-    rounds++;
-    if (nchunk == 0) {  // (nchunk / live are rewritten only after the next round's first barrier)
-      if (!C.live) break;
-      continue;
-    }
-    const int my_chunk = req ? C.rchunk[c] : -1;
-    const int my_off = req ? C.rfirst[c] : 0;
-    // (e) evaluate chunk by chunk
-    for (int k = 0; k < nchunk; ++k) {
-      if (my_chunk == k) {
-        for (int i = 0; i < size; ++i) {
-          C.jreq[my_off + i] = c;
-          C.jidx[my_off + i] = i;
-        }
-      }
-      __syncthreads();
-      const int njobs = C.chunk_jobs[k];
-      const int per = (njobs + 3) >> 2;  // slots per wavefront in the per-texture steps
-      const int t = wave * per + lane;
-      const bool mine = lane < per && t < njobs;
-      if (mine) tex_setup<WS>(s, C, t);
-      __syncthreads();
-      tex_gather<WS, WG_THREADS>(s, C, njobs, tid);
-      __syncthreads();
-      if (mine && C.jvalid[t]) tex_moments<WS>(C, t);
-      __syncthreads();
-      tex_scale<WS, WG_THREADS>(C, njobs, tid);
-      __syncthreads();
-      if (mine && C.jidx[t] >= 1) tex_dot<WS>(C, t);
-      __syncthreads();
-      chunks++;
-      grabs += njobs;
-      if (my_chunk == k) fv = request_value(s, C, my_off, size, need, jobs[cand], tex_valid);
-      __syncthreads();
-    }
-    // (f) consume the results
-    if (req) {
-      if (need == 1) {
-        evals++;
-        nevals++;
-        need = 0;
-      } else {
-        RefineJob& J = jobs[cand];
-        J.ncc = (float)(1.0 - (double)unrobustincc((float)fv));
-        for (int i = 0; i < 4; ++i) { J.rcoord[i] = fcoord[i]; J.rnormal[i] = fnormal[i]; }
-        cand = -1;
-        need = 0;
-      }
-    }
-  }
-  // per-wavefront reduction of the chain counters, one atomic each
-  for (int d = 32; d >= 1; d >>= 1) {
-    tex_valid += __shfl_xor(tex_valid, d);
-    nevals += __shfl_xor(nevals, d);
-  }
-  if (lane == 0 && wave < OW) {
-    atomicAdd(&st->evals, nevals);
-    atomicAdd(&st->tex_valid, tex_valid);
-    atomicAdd(&st->tex_valid_wg, tex_valid);
-  }
-  if (tid == 0) {
-    atomicAdd(&st->tex_grabs, grabs);
-    atomicAdd(&st->rounds, rounds);
-    atomicAdd(&st->chunks, chunks);
     atomicMax(&st->t_last, __builtin_amdgcn_s_memrealtime());
   }
 }
@@ -1751,39 +1506,17 @@ __global__ void angles_kernel(RefineJob* __restrict__ jobs, const double2* __res
   jobs[i].x0[2] = ang[i].y;
 }
 
+// Device arrays: max(n, 4096) elements exactly, contents discarded (every batch rewrites them).
 hipError_t RefineHost::ensure(size_t n) {
-  if (n <= cap) return hipSuccess;
-  release();
-  cap = std::max(n, (size_t)4096);
-  hipError_t e = hipMalloc((void**)&d_enc, cap * sizeof(float4));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_ang, cap * sizeof(double2));
-  if (e == hipSuccess) e = hipHostMalloc((void**)&h_enc, cap * sizeof(float4));
-  if (e == hipSuccess) e = hipHostMalloc((void**)&h_ang, cap * sizeof(double2));
-  if (e != hipSuccess) cap = 0;
+  const size_t m = std::max(n, (size_t)4096);
+  hipError_t e = d_enc.grow(m);
+  if (e == hipSuccess) e = d_ang.grow(m);
+  if (e == hipSuccess) e = h_enc.ensure(m * sizeof(float4));
+  if (e == hipSuccess) e = h_ang.ensure(m * sizeof(double2));
   return e;
 }
-void RefineHost::release() {
+RefineHost::~RefineHost() {
   if (ev_pre) (void)hipEventDestroy(ev_pre);
-  ev_pre = nullptr;
-  if (d_enc) (void)hipFree(d_enc);
-  if (d_ang) (void)hipFree(d_ang);
-  if (h_enc) (void)hipHostFree(h_enc);
-  if (h_ang) (void)hipHostFree(h_ang);
-  d_enc = nullptr; d_ang = nullptr; h_enc = nullptr; h_ang = nullptr;
-  cap = 0;
-}
-
-// refine_v2_kernel instantiations (texture slots * 100 + chains per wavefront)
-bool refine_config_supported(int tslots) {
-  switch (tslots) {
-    case 804: case 807: case 808: case 1201: case 1202: case 1203: case 1204: case 1206: case 1608: case 2408: return true;
-    case 164011: case 164021: case 164041: case 148041: case 132022: case 132042: case 116042: return true;
-#if defined(BQ_PRIVATE)
-    case 1264: case 2464: case 1232: case 2432: case 1216: case 2448: case 3232: case 3248: case 3264: case 4832:
-    case 4864: return true;
-#endif
-    default: return refine_split_supported(tslots) || refine_lane_supported(tslots);
-  }
 }
 
 static bool refine_tail_on() {
@@ -1791,35 +1524,28 @@ static bool refine_tail_on() {
   return on;
 }
 
-// Diagnostics only (PMVS_DUMP_JOBS=<file>, tools/r06ad.sh): after the first four refine batches of at
-// least 50 000 candidates, every refined job's preProcess outputs and its evaluation count are
-// appended to <file> as float32 rows [batch, nimg, evals, refine_code, dscale, ascale, x0[0..2],
-// weights[0..5], ncc] -- the data for a chain-length predictor.
-static void dump_jobs(const RefineJob* d_jobs, int n, hipStream_t stream) {
-  static const char* path = getenv("PMVS_DUMP_JOBS");
-  static int batches = 0;
-  if (!path || n < 50000 || batches >= 4) return;
-  std::vector<RefineJob> h((size_t)n);
-  if (hipStreamSynchronize(stream) != hipSuccess ||
-      hipMemcpy(h.data(), d_jobs, (size_t)n * sizeof(RefineJob), hipMemcpyDeviceToHost) != hipSuccess)
-    return;
-  FILE* f = fopen(path, "ab");
-  if (!f) return;
-  for (const RefineJob& J : h) {
-    if (J.status != PMVS_ACCEPTED) continue;
-    float r[16] = {(float)batches, (float)J.nimg, (float)J.evals, (float)J.refine_code, J.dscale, J.ascale,
-                   (float)J.x0[0], (float)J.x0[1], (float)J.x0[2], 0, 0, 0, 0, 0, 0, J.ncc};
-    for (int i = 0; i < 6 && i < PMVS_MAX_TAU; ++i) r[9 + i] = J.weights[i];
-    fwrite(r, sizeof(r), 1, f);
+// The wavefront form on a persistent grid of at most refine_grid single-wave workgroups.
+template <int WS>
+static hipError_t launch_wave_ws(const RefineLayout& l, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st,
+                                 int refine_grid, hipStream_t stream) {
+  const int need = (n + l.nc - 1) / l.nc;
+  const int rg = refine_grid < need ? refine_grid : need;
+  switch (l.config) {
+#define PMVS_WAVE_LAUNCH(TS, NC)                                                                                     \
+  case wave_config(TS, NC):                                                                                          \
+    hipLaunchKernelGGL((refine_v2_kernel<WS, TS, NC>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); \
+    break;
+    PMVS_WAVE_LAYOUTS(PMVS_WAVE_LAUNCH)
+#undef PMVS_WAVE_LAUNCH
+    default: return hipErrorInvalidValue;
   }
-  fclose(f);
-  ++batches;
+  return hipGetLastError();
 }
 
 template <int WS>
 static hipError_t launch_refine_ws(const DScene& s, const pmvs_candidate* d_in, RefineJob* d_jobs, pmvs_refined* d_out,
-                                   int n, DevStats* d_st, int grid, int refine_grid, int tslots, hipStream_t stream,
-                                   hipEvent_t* ev, RefineHost& rh) {
+                                   int n, DevStats* d_st, int grid, int refine_grid, const RefineLayout& asked,
+                                   hipStream_t stream, hipEvent_t* ev, RefineHost& rh) {
   // pre / post: the persistent grid (2 single-wave workgroups per SIMD) scaled to their residency
   const int gp = grid * PMVS_PREPOST_WPE / 2;
   const int g = gp < n ? gp : n;
@@ -1827,109 +1553,37 @@ static hipError_t launch_refine_ws(const DScene& s, const pmvs_candidate* d_in, 
   hipError_t e = rh.ensure((size_t)n);
   if (e != hipSuccess) return e;
   (void)hipEventRecord(ev[0], stream);
-  hipLaunchKernelGGL((pre_kernel<WS>), dim3(gpre), dim3(64), 0, stream, s, d_in, d_jobs, rh.d_enc, n, d_st);
+  hipLaunchKernelGGL((pre_kernel<WS>), dim3(gpre), dim3(64), 0, stream, s, d_in, d_jobs, rh.d_enc.p, n, d_st);
   if (rh.prof && (rh.ev_pre || hipEventCreate(&rh.ev_pre) == hipSuccess)) (void)hipEventRecord(rh.ev_pre, stream);
   // the start point's angles with the host's libm (encode_angles_host): one round trip per batch
-  if ((e = hipMemcpyAsync(rh.h_enc, rh.d_enc, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+  float4* const h_enc = rh.h_enc.as<float4>();
+  double2* const h_ang = rh.h_ang.as<double2>();
+  if ((e = hipMemcpyAsync(h_enc, rh.d_enc.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, stream)) != hipSuccess ||
       (e = hipStreamSynchronize(stream)) != hipSuccess)
     return e;
-  encode_angles_host(rh.h_enc, n, s.ascale, rh.h_ang);
-  if ((e = hipMemcpyAsync(rh.d_ang, rh.h_ang, (size_t)n * sizeof(double2), hipMemcpyHostToDevice, stream)) != hipSuccess)
+  encode_angles_host(h_enc, n, s.ascale, h_ang);
+  if ((e = hipMemcpyAsync(rh.d_ang.p, h_ang, (size_t)n * sizeof(double2), hipMemcpyHostToDevice, stream)) != hipSuccess)
     return e;
-  hipLaunchKernelGGL(angles_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_jobs, rh.d_ang, rh.d_enc, n);
+  hipLaunchKernelGGL(angles_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_jobs, rh.d_ang.p, rh.d_enc.p, n);
   (void)hipEventRecord(ev[1], stream);
   if (rh.prof && rh.ev_pre && hipEventSynchronize(ev[1]) == hipSuccess) {  // diagnostics only: one more wait
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, rh.ev_pre, ev[1]) == hipSuccess) rh.trip_ms += ms;
     ++rh.trips;
   }
-  if (tslots >= 300000) {  // lane form (pmvs_refine_lane.hip)
-    if ((e = launch_refine_lane(tslots, s, d_jobs, n, d_st, stream)) != hipSuccess) return e;
-    if (refine_tail_on()) hipLaunchKernelGGL(refine_tail_kernel, dim3(1), dim3(64), 0, stream, d_st, 1);
-    (void)hipEventRecord(ev[2], stream);
-    hipLaunchKernelGGL((post_kernel<WS>), dim3(g), dim3(64), 0, stream, s, d_jobs, d_out, n, d_st);
-    (void)hipEventRecord(ev[3], stream);
-    return hipGetLastError();
-  }
-  // (before the tau check below, which then also applies to the fallback layout)
-  if (tslots >= 200000 && tslots < 300000 && WS > 7) tslots = 1206;  // split form: a texture's 3 * 81 samples exceed its registers
-  // a request's textures must fit one chunk (TSLOTS >= tau, tau <= PMVS_MAX_TAU = 16): smaller
-  // chunk configs are only valid for small tau, otherwise the default 24-slot kernel runs
-  if (tslots / 100 < s.tau) {
-    tslots = 2408;
-    refine_grid = refine_grid / 2 > 0 ? refine_grid / 2 : 1;  // 39 KB LDS: 4 resident per CU
-  }
-  const int nc = tslots % 100;
-  const int rg = refine_grid < (n + nc - 1) / nc ? refine_grid : (n + nc - 1) / nc;
-  if (tslots >= 200000) {  // split form (pmvs_refine_split.hip)
-    if ((e = launch_refine_split(tslots, s, d_jobs, n, d_st, stream, rh.bq_cold)) != hipSuccess) return e;
-    if (refine_tail_on()) hipLaunchKernelGGL(refine_tail_kernel, dim3(1), dim3(64), 0, stream, d_st, 0);
-    (void)hipEventRecord(ev[2], stream);
-    hipLaunchKernelGGL((post_kernel<WS>), dim3(g), dim3(64), 0, stream, s, d_jobs, d_out, n, d_st);
-    (void)hipEventRecord(ev[3], stream);
-    dump_jobs(d_jobs, n, stream);
-    return hipGetLastError();
-  }
-  if (tslots >= 100000) {  // workgroup form: 100000 + chains * 1000 + optimizer wavefronts * 10 + workgroups per CU
-    const int ncw = (tslots / 1000) % 100, wgpc = tslots % 10;
-    int dev = 0, cus = 0;
-    if ((e = hipGetDevice(&dev)) != hipSuccess ||
-        (e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess)
-      return e;
-    cus = cus > 0 ? cus : 1;
-    // every CU gets a workgroup while the batch has candidates for them; a small batch runs fewer
-    // chains per workgroup (nc_active) rather than fewer workgroups: its length is one chain's latency
-    const int wgrid = cus * wgpc < n ? cus * wgpc : n;
-    const int nca = (n + wgrid - 1) / wgrid < ncw ? (n + wgrid - 1) / wgrid : ncw;
-#define PMVS_WG(NCc, OWc, WGPCc)                                                                                    \
-  case 100000 + NCc * 1000 + OWc * 10 + WGPCc:                                                                       \
-    hipLaunchKernelGGL((refine_wg_kernel<WS, NCc, RefWgFit<WS, NCc, WGPCc>::slots, OWc>), dim3(wgrid), dim3(WG_THREADS), \
-                       0, stream, s, d_jobs, n, nca, d_st);                                                           \
-    break;
-    switch (tslots) {
-      PMVS_WG(64, 1, 1)
-      PMVS_WG(64, 2, 1)
-      PMVS_WG(64, 4, 1)
-      PMVS_WG(48, 4, 1)
-      PMVS_WG(32, 2, 2)
-      PMVS_WG(32, 4, 2)
-      PMVS_WG(16, 4, 2)
-      default: return hipErrorInvalidValue;
+  const RefineLayout l = resolve(asked, WS, s.tau);
+  switch (l.form) {
+    case RefineForm::Lane: e = launch_refine_lane(l, s, d_jobs, n, d_st, stream); break;
+    case RefineForm::Split: e = launch_refine_split(l, s, d_jobs, n, d_st, stream, rh.bq_cold); break;
+    case RefineForm::Wave: {
+      const int rgrid = refine_grid / l.grid_div > 0 ? refine_grid / l.grid_div : 1;
+      e = launch_wave_ws<WS>(l, s, d_jobs, n, d_st, rgrid, stream);
+      break;
     }
-#undef PMVS_WG
-    if (refine_tail_on()) hipLaunchKernelGGL(refine_tail_kernel, dim3(1), dim3(64), 0, stream, d_st, 1);
-    (void)hipEventRecord(ev[2], stream);
-    hipLaunchKernelGGL((post_kernel<WS>), dim3(g), dim3(64), 0, stream, s, d_jobs, d_out, n, d_st);
-    (void)hipEventRecord(ev[3], stream);
-    return hipGetLastError();
   }
-  // tslots = texture slots per objective chunk * 100 + optimizer chains per wavefront
-  switch (tslots) {
-    case 804: hipLaunchKernelGGL((refine_v2_kernel<WS, 8, 4>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-    case 808: hipLaunchKernelGGL((refine_v2_kernel<WS, 8, 8>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-    case 807: hipLaunchKernelGGL((refine_v2_kernel<WS, 8, 7>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-    case 1608: hipLaunchKernelGGL((refine_v2_kernel<WS, 16, 8>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-    case 2408: hipLaunchKernelGGL((refine_v2_kernel<WS, 24, 8>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-    case 1204: hipLaunchKernelGGL((refine_v2_kernel<WS, 12, 4>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-    case 1201: hipLaunchKernelGGL((refine_v2_kernel<WS, 12, 1>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-    case 1202: hipLaunchKernelGGL((refine_v2_kernel<WS, 12, 2>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-    case 1203: hipLaunchKernelGGL((refine_v2_kernel<WS, 12, 3>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-#if defined(BQ_PRIVATE)
-    case 1264: hipLaunchKernelGGL((refine_v2_kernel<WS, 12, 64>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-    case 2464: hipLaunchKernelGGL((refine_v2_kernel<WS, 24, 64>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-    case 1232: hipLaunchKernelGGL((refine_v2_kernel<WS, 12, 32>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-    case 2432: hipLaunchKernelGGL((refine_v2_kernel<WS, 24, 32>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-    case 1216: hipLaunchKernelGGL((refine_v2_kernel<WS, 12, 16>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-    case 2448: hipLaunchKernelGGL((refine_v2_kernel<WS, 24, 48>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-    case 3232: hipLaunchKernelGGL((refine_v2_kernel<WS, 32, 32>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-    case 3248: hipLaunchKernelGGL((refine_v2_kernel<WS, 32, 48>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-    case 3264: hipLaunchKernelGGL((refine_v2_kernel<WS, 32, 64>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-    case 4832: hipLaunchKernelGGL((refine_v2_kernel<WS, 48, 32>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-    case 4864: hipLaunchKernelGGL((refine_v2_kernel<WS, 48, 64>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-#endif
-    default: hipLaunchKernelGGL((refine_v2_kernel<WS, 12, 6>), dim3(rg), dim3(64), 0, stream, s, d_jobs, n, d_st); break;
-  }
-  if (refine_tail_on()) hipLaunchKernelGGL(refine_tail_kernel, dim3(1), dim3(64), 0, stream, d_st, 0);
+  if (e != hipSuccess) return e;
+  if (refine_tail_on())
+    hipLaunchKernelGGL(refine_tail_kernel, dim3(1), dim3(64), 0, stream, d_st, l.form == RefineForm::Lane ? 1 : 0);
   (void)hipEventRecord(ev[2], stream);
   hipLaunchKernelGGL((post_kernel<WS>), dim3(g), dim3(64), 0, stream, s, d_jobs, d_out, n, d_st);
   (void)hipEventRecord(ev[3], stream);
@@ -1937,13 +1591,13 @@ static hipError_t launch_refine_ws(const DScene& s, const pmvs_candidate* d_in, 
 }
 
 hipError_t launch_refine(const DScene& s, const pmvs_candidate* d_in, RefineJob* d_jobs, pmvs_refined* d_out, int n,
-                         DevStats* d_st, int grid, int refine_grid, int tslots, hipStream_t stream, hipEvent_t* ev,
-                         RefineHost& rh) {
+                         DevStats* d_st, int grid, int refine_grid, const RefineLayout& layout, hipStream_t stream,
+                         hipEvent_t* ev, RefineHost& rh) {
   if (n <= 0) return hipSuccess;
   switch (s.wsize) {
-    case 5: return launch_refine_ws<5>(s, d_in, d_jobs, d_out, n, d_st, grid, refine_grid, tslots, stream, ev, rh);
-    case 7: return launch_refine_ws<7>(s, d_in, d_jobs, d_out, n, d_st, grid, refine_grid, tslots, stream, ev, rh);
-    case 9: return launch_refine_ws<9>(s, d_in, d_jobs, d_out, n, d_st, grid, refine_grid, tslots, stream, ev, rh);
+    case 5: return launch_refine_ws<5>(s, d_in, d_jobs, d_out, n, d_st, grid, refine_grid, layout, stream, ev, rh);
+    case 7: return launch_refine_ws<7>(s, d_in, d_jobs, d_out, n, d_st, grid, refine_grid, layout, stream, ev, rh);
+    case 9: return launch_refine_ws<9>(s, d_in, d_jobs, d_out, n, d_st, grid, refine_grid, layout, stream, ev, rh);
     default: return hipErrorInvalidValue;
   }
 }
@@ -2226,15 +1880,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BQ_CALLER_WP
                                                         double* __restrict__ out) {
   const int lane = threadIdx.x;
   const int i = blockIdx.x * C + lane;
-#if defined(BQ_PRIVATE)
-  BqState st_priv;
-  if (lane >= C || i >= n) return;
-  BQ_AS BqState& st = *(BQ_AS BqState*)&st_priv;
-#else
   __shared__ BqState sts[C];
   if (lane >= C || i >= n) return;
   BQ_AS BqState& st = *(BQ_AS BqState*)&sts[lane];
-#endif
   const double lb[3] = {-HUGE_VAL, -23.99999, -23.99999}, ub[3] = {HUGE_VAL, 23.99999, 23.99999};
   double x[3] = {x0[3 * i], x0[3 * i + 1], x0[3 * i + 2]};
   bq_begin(st, x, lb, ub, 1e-7, maxeval);
@@ -2250,11 +1898,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BQ_CALLER_WP
 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BQ_CALLER_WPE))) void bobyqa_wave_kernel(int kind, const double* __restrict__ x0, int n, int maxeval,
                                                          double* __restrict__ out) {
-#if defined(BQ_PRIVATE)
-  BqState st_;  // lane 0's
-#else
   __shared__ BqState st_;
-#endif
   BQ_AS BqState& st = *(BQ_AS BqState*)&st_;
   __shared__ int stepv;
   __shared__ double fres, xes[3];

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "pmvs_device.h"
 #include "pmvs_devbuf.h"
+#include "pmvs_refine_layouts.h"
 #include <functional>
 #include <memory>
 #include <utility>
@@ -22,14 +23,43 @@ inline hipError_t memset_big(void* p, int value, size_t bytes, hipStream_t st) {
   }
   return hipSuccess;
 }
-bool refine_config_supported(int tslots);  // PMVS_REFINE_CONFIG values this build instantiates
+// Page-locked host staging (hipHostMalloc), grown on demand with 25 % headroom: the large per-pass
+// downloads (filterSmallGroups' edge lists, the expansion queue's initial order) and the refine batches'
+// start points at full PCIe rate.
+struct PinnedBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  PinnedBuf() = default;
+  PinnedBuf(PinnedBuf&& o) noexcept : p(o.p), cap(o.cap) {
+    o.p = nullptr;
+    o.cap = 0;
+  }
+  PinnedBuf& operator=(PinnedBuf&& o) noexcept {  // o leaves with the old buffer and frees it
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+    return *this;
+  }
+  hipError_t ensure(size_t bytes) {
+    if (bytes <= cap && p) return hipSuccess;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+    const size_t c = bytes + bytes / 4 + 4096;
+    const hipError_t e = hipHostMalloc(&p, c, hipHostMallocDefault);
+    if (e == hipSuccess) cap = c;
+    return e;
+  }
+  template <class T>
+  T* as(size_t offset_bytes = 0) const { return reinterpret_cast<T*>(static_cast<char*>(p) + offset_bytes); }
+  ~PinnedBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+};
 // Host staging of the refine batches' start-point angles (encode_angles_host, pmvs_kernels.hip).
 struct RefineHost {
-  float4* d_enc = nullptr;
-  double2* d_ang = nullptr;
-  float4* h_enc = nullptr;   // pinned
-  double2* h_ang = nullptr;  // pinned
-  size_t cap = 0;
+  DevBuf<float4> d_enc;
+  DevBuf<double2> d_ang;
+  PinnedBuf h_enc, h_ang;
   DevBuf<unsigned char> bq_cold;  // the split-form refine kernel's cold optimizer state (launch_refine_split)
   // PMVS_EXPAND_PROFILE: the round trip's share of the device timeline (pre_kernel's end to the
   // refine kernel's start: start points down, host libm, angles up), summed over the batches
@@ -38,27 +68,25 @@ struct RefineHost {
   double trip_ms = 0.0;
   long long trips = 0;
   hipError_t ensure(size_t n);
-  void release();
-  ~RefineHost() { release(); }
+  ~RefineHost();
 };
 // Waves per SIMD pre_kernel / post_kernel / filter_refimage_kernel are built for (PMVS_PREPOST_WPE, default 3:
 // pmvs_kernels.hip); their persistent grid is the scene grid x this / 2, and the per-workgroup global scratch is
 // sized for it.
 int prepost_waves();
+// pre, the angle round trip, the refine kernel of resolve(layout, wsize, tau) (pmvs_refine_layouts.h), post
 hipError_t launch_refine(const DScene& s, const pmvs_candidate* d_in, RefineJob* d_jobs, pmvs_refined* d_out, int n,
-                         DevStats* d_st, int grid, int refine_grid, int tslots, hipStream_t stream, hipEvent_t* ev,
-                         RefineHost& rh);
-// split-form refine kernel alone (pmvs_refine_split.hip), config 200000 + optimizer wavefronts * 1000 +
-// chains per optimizer wavefront, wsize 5 or 7
-bool refine_split_supported(int config);
-// `cold`: the chains' cold optimizer state (bobyqa_dev.h BqCold), grown here to one slot per chain of a
-// full grid; it carries nothing from one launch to the next
-hipError_t launch_refine_split(int config, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st, hipStream_t stream,
-                               DevBuf<unsigned char>& cold);
-// lane-form refine kernel (pmvs_refine_lane.hip): one candidate per wavefront, BOBYQA state spread over
-// the lanes; config 300000 (lanes per texture from tau), 300004, 300008
-bool refine_lane_supported(int config);
-hipError_t launch_refine_lane(int config, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st, hipStream_t stream);
+                         DevStats* d_st, int grid, int refine_grid, const RefineLayout& layout, hipStream_t stream,
+                         hipEvent_t* ev, RefineHost& rh);
+// split-form refine kernel alone (pmvs_refine_split.hip), wsize 5 or 7.  `cold`: the chains' cold optimizer
+// state (bobyqa_dev.h BqCold), grown here to one slot per chain of a full grid; it carries nothing from
+// one launch to the next
+hipError_t launch_refine_split(const RefineLayout& l, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st,
+                               hipStream_t stream, DevBuf<unsigned char>& cold);
+// lane-form refine kernel alone (pmvs_refine_lane.hip): one candidate per wavefront, BOBYQA state spread
+// over the lanes; a resolved layout (4 or 8 lanes per texture)
+hipError_t launch_refine_lane(const RefineLayout& l, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st,
+                              hipStream_t stream);
 hipError_t launch_incc_eval(const DScene& s, const pmvs_eval_query* d_q, int n, double* d_out, DevStats* d_st,
                             hipStream_t stream);
 hipError_t launch_grab_tex(const DScene& s, const pmvs_tex_query* d_q, int n, float* d_out, int* d_valid,
@@ -126,37 +154,6 @@ hipError_t depth_map_pass(const DScene& s, const pmvs_patch* P, int n, const int
                           long long cells, const DepthMapArrays& out, hipStream_t st);
 
 // ---- filter pass (pmvs_filter.hip)
-// Page-locked host staging (hipHostMalloc), grown on demand: the large per-pass downloads
-// (filterSmallGroups' edge lists, the expansion queue's initial order) at full PCIe rate.
-struct PinnedBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  PinnedBuf() = default;
-  PinnedBuf(PinnedBuf&& o) noexcept : p(o.p), cap(o.cap) {
-    o.p = nullptr;
-    o.cap = 0;
-  }
-  PinnedBuf& operator=(PinnedBuf&& o) noexcept {  // o leaves with the old buffer and frees it
-    std::swap(p, o.p);
-    std::swap(cap, o.cap);
-    return *this;
-  }
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t c = bytes + bytes / 4 + 4096;
-    const hipError_t e = hipHostMalloc(&p, c, hipHostMallocDefault);
-    if (e == hipSuccess) cap = c;
-    return e;
-  }
-  template <class T>
-  T* as(size_t offset_bytes = 0) const { return reinterpret_cast<T*>(static_cast<char*>(p) + offset_bytes); }
-  ~PinnedBuf() {
-    if (p) (void)hipHostFree(p);
-  }
-};
 // The fields of a patch that neighbour and visibility tests read from OTHER patches (isNeighbor,
 // computeGain, isVisible), one 64-B line per patch instead of 2-3 lines of its 1.6-KB record;
 // rebuilt by every collect and written by the expansion's commit (coord / normal / dscale / ncc

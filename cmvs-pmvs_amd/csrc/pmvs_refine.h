@@ -1,5 +1,5 @@
 // pmvs_refine.h -- device pieces of refinePatchBFGS shared by the refine kernels' translation units
-// (pmvs_kernels.hip: pre / wavefront / workgroup forms and post; pmvs_refine_split.hip: split form).
+// (pmvs_kernels.hip: pre / wavefront form / post; pmvs_refine_split.hip: split form; pmvs_refine_lane.hip: lane form).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -229,37 +229,6 @@ __device__ __forceinline__ double lane_request(const DScene& s, const float* geo
   return f;
 }
 
-// One objective request out of line (LANE_EVAL_CALL): decode, getPAxes and lane_request from the job
-// record, so the evaluation's code exists once instead of once per CALFUN site of the optimizer (4
-// copies inlined), and its registers are allocated apart from the optimizer's.
-#ifndef LANE_EVAL_CALL
-#define LANE_EVAL_CALL 0
-#endif
-struct LaneEval {
-  double f;
-  unsigned nvalid;
-};
-template <int WS, int LP>
-__device__ __noinline__ LaneEval lane_eval(const DScene& s, const RefineJob* __restrict__ J, double x0, double x1,
-                                           double x2, int need, int myview, int size) {
-  RefineSetup R;
-  for (int i = 0; i < 4; ++i) { R.center[i] = J->center[i]; R.ray[i] = J->ray[i]; }
-  R.dscale = J->dscale;
-  R.ascale = s.ascale;
-  R.ref = __builtin_amdgcn_readfirstlane(J->images[0]);
-  const double xe[3] = {x0, x1, x2};
-  float fc[4], fn[4], geo[16], px[4], py[4];
-  decode(s, R, xe, fc, fn);
-  get_paxes(s, s.views[R.ref], fc, fn, px, py);
-  for (int i = 0; i < 4; ++i) {
-    geo[i] = fc[i]; geo[4 + i] = fn[i];
-    geo[8 + i] = px[i]; geo[12 + i] = py[i];
-  }
-  unsigned long long tv = 0;
-  const double f = lane_request<WS, LP>(s, geo, myview, size, need, *J, tv);
-  return {f, (unsigned)tv};
-}
-
 // One wavefront per candidate, persistent: candidates from the launch's queue (DevStats::queue2), the
 // ones preProcess rejected skipped.
 template <int WS, int LP>
@@ -316,17 +285,9 @@ __global__ __launch_bounds__(LANE_THREADS) __attribute__((amdgpu_waves_per_eu(LA
 #if defined(LANE_PROFILE)
       const unsigned long long t0 = __builtin_amdgcn_s_memtime();
 #endif
-#if LANE_EVAL_CALL
-      const LaneEval e = lane_eval<WS, LP>(s, &J, xe[0], xe[1], xe[2], 1, myview, size);
-      tex_valid += e.nvalid;
-      grabs += size;
-      ++nreq;
-      const double fv = e.f;
-#else
       float fc[4], fn[4];
       decode(s, R, xe, fc, fn);
       const double fv = request(fc, fn, 1);
-#endif
 #if defined(LANE_PROFILE)
       const unsigned long long t1 = __builtin_amdgcn_s_memtime();
       prof_eval += t1 - t0;
@@ -358,14 +319,7 @@ __global__ __launch_bounds__(LANE_THREADS) __attribute__((amdgpu_waves_per_eu(LA
       if (nimg < 2)  // computeINCC returns 2.0 without grabbing (optim.cpp:866)
         ncc = (float)(1.0 - (double)unrobustincc(2.0f));
       else {  // final computeINCC (robust, weighted) at the refined geometry
-#if LANE_EVAL_CALL
-        const LaneEval e = lane_eval<WS, LP>(s, &J, xo[0], xo[1], xo[2], 2, myview, size);
-        grabs += size;
-        ++nreq;
-        ncc = (float)(1.0 - (double)unrobustincc((float)e.f));
-#else
         ncc = (float)(1.0 - (double)unrobustincc((float)request(fc, fn, 2)));
-#endif
       }
     }
     if (lane == 0) {
@@ -396,16 +350,10 @@ __global__ __launch_bounds__(LANE_THREADS) __attribute__((amdgpu_waves_per_eu(LA
   }
 }
 
-// config 300000 + LP: the lane form with LP lanes per texture (4: up to 16 textures per request, 8: up
-// to 8); 300000 picks LP from the scene's tau
-bool refine_lane_supported(int config) { return config == 300000 || config == 300004 || config == 300008; }
-
 template <int WS>
-static hipError_t launch_lane_ws(int config, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st, hipStream_t stream) {
-  int lp = config % 100;
-  if (lp == 0) lp = s.tau <= 8 ? 8 : 4;
-  if (WAVE / lp < s.tau) lp = 4;
-  if (WAVE / lp < s.tau) return hipErrorInvalidValue;
+static hipError_t launch_lane_ws(const RefineLayout& l, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st,
+                                 hipStream_t stream) {
+  if (l.lp <= 0 || WAVE / l.lp < s.tau) return hipErrorInvalidValue;  // resolve() picks lanes per texture that hold tau
   int dev = 0, cus = 0;
   hipError_t e;
   if ((e = hipGetDevice(&dev)) != hipSuccess ||
@@ -422,19 +370,25 @@ static hipError_t launch_lane_ws(int config, const DScene& s, RefineJob* d_jobs,
   const int waves = cus * 4 * wps;
   const int need = (n + 3) / 4;
   const int grid = need < waves / 4 ? need : waves / 4;
-  if (lp == 8)
-    hipLaunchKernelGGL((refine_lane_kernel<WS, 8>), dim3(grid), dim3(LANE_THREADS), 0, stream, s, d_jobs, n, d_st);
-  else
-    hipLaunchKernelGGL((refine_lane_kernel<WS, 4>), dim3(grid), dim3(LANE_THREADS), 0, stream, s, d_jobs, n, d_st);
+  switch (l.config) {
+#define PMVS_LANE_LAUNCH(LPc)                                                                                        \
+  case lane_config(LPc):                                                                                             \
+    hipLaunchKernelGGL((refine_lane_kernel<WS, LPc>), dim3(grid), dim3(LANE_THREADS), 0, stream, s, d_jobs, n, d_st); \
+    break;
+    PMVS_LANE_LAYOUTS(PMVS_LANE_LAUNCH)
+#undef PMVS_LANE_LAUNCH
+    default: return hipErrorInvalidValue;  // kLaneAuto: not resolved
+  }
   return hipGetLastError();
 }
 
-hipError_t launch_refine_lane(int config, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st, hipStream_t stream) {
+hipError_t launch_refine_lane(const RefineLayout& l, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st,
+                              hipStream_t stream) {
   if (n <= 0) return hipSuccess;
   switch (s.wsize) {
-    case 5: return launch_lane_ws<5>(config, s, d_jobs, n, d_st, stream);
-    case 7: return launch_lane_ws<7>(config, s, d_jobs, n, d_st, stream);
-    case 9: return launch_lane_ws<9>(config, s, d_jobs, n, d_st, stream);
+    case 5: return launch_lane_ws<5>(l, s, d_jobs, n, d_st, stream);
+    case 7: return launch_lane_ws<7>(l, s, d_jobs, n, d_st, stream);
+    case 9: return launch_lane_ws<9>(l, s, d_jobs, n, d_st, stream);
     default: return hipErrorInvalidValue;
   }
 }

@@ -50,15 +50,11 @@ namespace pmvsdev {
 // `avail` (chunks not yet claimed: set by the group's atomic exchange after its tables are written,
 // taken by atomic decrements; a stale decrement only drives it below 0) and `done` (chunks
 // evaluated).  No workgroup barrier after the start.  DESIGN.md §5c.
-// Wavefronts per SIMD (register budget) and workgroup size: 2 and 512 (8 wavefronts, 256 VGPRs); an
-// experiment build (SPLIT_WPE=1, SPLIT_THREADS=256) gives 4 wavefronts 512 registers each.
+// Wavefronts per SIMD (register budget) and workgroup size: 2 and 512 (8 wavefronts, 256 VGPRs).
 #ifndef SPLIT_WPE
 #define SPLIT_WPE 2
 #endif
-#ifndef SPLIT_THREADS_
-#define SPLIT_THREADS_ 512
-#endif
-constexpr int SPLIT_THREADS = SPLIT_THREADS_;
+constexpr int SPLIT_THREADS = 512;
 constexpr int SPLIT_TS = 64;  // texture slots per chunk at most (LP = 1)
 
 template <int WS, int G, int CG>
@@ -227,7 +223,7 @@ __device__ __forceinline__ unsigned long long split_chunk_body(const DScene& s, 
   const int src = rt * LP + sub;
   const int refok = __shfl(T.ok, src);
   float ans = 0.0f;
-#if !defined(SPLIT_DOT_STREAM)  // the reference texture's samples pulled at once (A/B r05m: equal)
+  // the reference texture's samples pulled at once (reading them one at a time was equal: A/B r05m)
   float px[K], py[K], pz[K];
 #pragma unroll
   for (int q = 0; q < K; ++q) { px[q] = __shfl(X[q], src); py[q] = __shfl(Y[q], src); pz[q] = __shfl(Z[q], src); }
@@ -247,29 +243,6 @@ __device__ __forceinline__ unsigned long long split_chunk_body(const DScene& s, 
       if (sub == j + 1) ans = u;
     }
   }
-#else
-#pragma unroll
-  for (int j = 0; j < LP; ++j) {
-    // stage j: the lanes with sub == j, whose reference lanes (same sub) are active with them, read the
-    // reference samples one at a time (no K-wide copy of them in registers)
-    if (sub == j) {
-#pragma unroll
-      for (int q = 0; q < K; ++q)
-        if (q < kn) {
-          const float px = __shfl(X[q], src), py = __shfl(Y[q], src), pz = __shfl(Z[q], src);
-          if (ok) {
-            ans += px * X[q];
-            ans += py * Y[q];
-            ans += pz * Z[q];
-          }
-        }
-    }
-    if (j + 1 < LP) {
-      const float u = __shfl_up(ans, 1);
-      if (sub == j + 1) ans = u;
-    }
-  }
-#endif
   if (mine && sub == LP - 1) {
     float jr = 0.0f;
     if (idx >= 1 && refok && ok) jr = robustincc((float)(1.0 - (double)__fdiv_rn(ans, (float)(3 * S))));
@@ -506,11 +479,7 @@ __device__ __noinline__ void split_evaluator(const DScene& s, SPLIT_AS RefSplitL
       continue;
     }
     SP_MARK(7);
-#if defined(SPLIT_EVAL_CALL)
-    tex_valid += split_chunk<WS, G, CG, LP>(s, C, jobs, g, k, prof);
-#else
     tex_valid += split_chunk_body<WS, G, CG, LP>(s, C, jobs, g, k, prof);
-#endif
     tprev = SP_NOW();
     grabs += C.choff[g][k + 1] - C.choff[g][k];
     chunks++;
@@ -552,29 +521,10 @@ __global__ __launch_bounds__(SPLIT_THREADS) __attribute__((amdgpu_waves_per_eu(S
 }
 
 
-// config = 200000 + LP * 10000 + optimizer wavefronts * 1000 + chains per optimizer wavefront, LP =
-// lanes per texture in the evaluators (0 reads as 1); WS <= 7.  The chains a CU holds (G * CG) are
-// bounded by LDS alone: 1512 B of BqHot and 142 B of tables per chain allow 96 (6 x 16, 5 x 19, 7 x 13).
-#if SPLIT_THREADS_ == 512
-#define PMVS_SPLIT_CONFIGS(X) X(0, 2, 32) X(0, 4, 16) X(2, 4, 16) X(2, 5, 16) X(2, 5, 19) X(2, 6, 12) X(2, 6, 14) X(2, 6, 15) \
-  X(2, 6, 16) X(2, 7, 12) X(2, 7, 13) X(2, 8, 10) X(3, 6, 14) X(4, 5, 16) X(4, 6, 14) X(4, 7, 12) X(4, 8, 10) X(8, 8, 10)
-#else
-#define PMVS_SPLIT_CONFIGS(X) X(2, 4, 20) X(4, 4, 20) X(8, 4, 20) X(2, 2, 40) X(4, 3, 24)
-#endif
-bool refine_split_supported(int config) {
-#define PMVS_SPLIT_CASE(LPc, Gc, CGc) case 200000 + LPc * 10000 + Gc * 1000 + CGc:
-  switch (config) {
-    PMVS_SPLIT_CONFIGS(PMVS_SPLIT_CASE)
-    return true;
-    default: return false;
-  }
-#undef PMVS_SPLIT_CASE
-}
-
 template <int WS>
-static hipError_t launch_split_ws(int config, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st, hipStream_t stream,
-                                  DevBuf<unsigned char>& cold) {
-  const int gw = (config / 1000) % 10, cg = config % 1000;
+static hipError_t launch_split_ws(const RefineLayout& l, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st,
+                                  hipStream_t stream, DevBuf<unsigned char>& cold) {
+  const int gw = l.g, cg = l.cg;
   int dev = 0, cus = 0;
   hipError_t e;
   if ((e = hipGetDevice(&dev)) != hipSuccess ||
@@ -587,25 +537,25 @@ static hipError_t launch_split_ws(int config, const DScene& s, RefineJob* d_jobs
   const int nca = per < cg ? per : cg;
   // a BqCold per chain of the largest grid; never read before the chain's bq_begin wrote it
   if ((e = cold.grow((size_t)cus * gw * cg * sizeof(BqCold))) != hipSuccess) return e;
+  switch (l.config) {
 #define PMVS_SPLIT_LAUNCH(LPc, Gc, CGc)                                                                                   \
-  case 200000 + LPc * 10000 + Gc * 1000 + CGc:                                                                             \
+  case split_config(LPc, Gc, CGc):                                                                                         \
     hipLaunchKernelGGL((refine_split_kernel<WS, Gc, CGc, (LPc > 0 ? LPc : 1)>), dim3(sgrid), dim3(SPLIT_THREADS), 0, stream, \
                        s, d_jobs, (BqCold*)cold.p, n, nca, d_st);                                                          \
     break;
-  switch (config) {
-    PMVS_SPLIT_CONFIGS(PMVS_SPLIT_LAUNCH)
+    PMVS_SPLIT_LAYOUTS(PMVS_SPLIT_LAUNCH)
+#undef PMVS_SPLIT_LAUNCH
     default: return hipErrorInvalidValue;
   }
-#undef PMVS_SPLIT_LAUNCH
   return hipGetLastError();
 }
 
-hipError_t launch_refine_split(int config, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st, hipStream_t stream,
-                               DevBuf<unsigned char>& cold) {
+hipError_t launch_refine_split(const RefineLayout& l, const DScene& s, RefineJob* d_jobs, int n, DevStats* d_st,
+                               hipStream_t stream, DevBuf<unsigned char>& cold) {
   if (n <= 0) return hipSuccess;
   switch (s.wsize) {
-    case 5: return launch_split_ws<5>(config, s, d_jobs, n, d_st, stream, cold);
-    case 7: return launch_split_ws<7>(config, s, d_jobs, n, d_st, stream, cold);
+    case 5: return launch_split_ws<5>(l, s, d_jobs, n, d_st, stream, cold);
+    case 7: return launch_split_ws<7>(l, s, d_jobs, n, d_st, stream, cold);
     default: return hipErrorInvalidValue;
   }
 }

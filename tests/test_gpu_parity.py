@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import small_scene
+from refine_configs import REFINE_CONFIGS, RETIRED_CONFIG
 
 pytestmark = pytest.mark.gpu
 
@@ -108,14 +109,11 @@ def test_refine_batch_bit_exact(scenes):
         assert sg[k] == so[k], k
 
 
-REFINE_CONFIGS = [300000, 300004, 300008, 1206, 2408, 164011, 164021, 164041, 148041, 132022, 132042, 116042, 202032, 224016, 225016, 226014, 227012, 228010, 245016, 246014, 248010]
-
-
-@pytest.mark.parametrize("config", REFINE_CONFIGS)
+@pytest.mark.parametrize("config", REFINE_CONFIGS + [RETIRED_CONFIG])
 def test_refine_configs_bit_exact(scenes, monkeypatch, config):
-    """Every refine-kernel layout (PMVS_REFINE_CONFIG: the wavefront form's texture slots * 100 +
-    chains, the workgroup form's 100000 + chains * 1000 + optimizer wavefronts * 10 + workgroups per
-    CU) gives the oracle's records, for a batch that fills the chip and for a 5-candidate one."""
+    """Every refine-kernel layout of tests/refine_configs.py (PMVS_REFINE_CONFIG: the numbering is in
+    pmvs_refine_layouts.h) gives the oracle's records, for a batch that fills the chip and for a
+    5-candidate one; so does a number that names no layout (RETIRED_CONFIG, which runs 1206)."""
     import pmvs_amd as P
     inp, p, g, o = scenes
     monkeypatch.setenv("PMVS_REFINE_CONFIG", str(config))

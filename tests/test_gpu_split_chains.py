@@ -6,12 +6,11 @@ import pytest
 import torch  # before libpmvs_amd.so is loaded (see test_gpu_loop_export.py); _full reads the CU count from it
 
 from conftest import small_scene
+from refine_configs import NEW_CONFIGS
 from test_gpu_parity import compare_refined
 
 pytestmark = pytest.mark.gpu
 
-# 200000 + lanes per texture * 10000 + optimizer wavefronts * 1000 + chains per optimizer wavefront
-NEW_CONFIGS = [226015, 226016, 225019, 227013]
 COUNTERS = ("accepted", "fail_pre", "fail_post", "refine_failed", "evals", "tex_valid")
 NMAX = 40000
 

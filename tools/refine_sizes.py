@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.join(ROOT, "cmvs-pmvs_amd"))
 import numpy as np  # noqa: E402
 import pmvs_amd as P  # noqa: E402
 
-cfgs = [int(c) for c in (sys.argv[1] if len(sys.argv) > 1 else "1206,132042").split(",")]
+cfgs = [int(c) for c in (sys.argv[1] if len(sys.argv) > 1 else "1206,225019").split(",")]
 sizes = [int(c) for c in (sys.argv[2] if len(sys.argv) > 2 else "2000,5000,10000,20000,40000,80000,120000").split(",")]
 t0 = time.time()
 inp, sp = P.synth_scene(50, 3840, 2160, level=0, supersample=2, nthreads=16, seed=0x504D5653)

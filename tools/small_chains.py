@@ -10,7 +10,7 @@ sys.path.insert(0, os.path.join(ROOT, "cmvs-pmvs_amd"))
 import numpy as np  # noqa: E402
 import pmvs_amd as P  # noqa: E402
 
-cfgs = [int(c) for c in (sys.argv[1] if len(sys.argv) > 1 else "132042,226014").split(",")]
+cfgs = [int(c) for c in (sys.argv[1] if len(sys.argv) > 1 else "300000,226014").split(",")]
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 2500
 inp, sp = P.synth_scene(50, 3840, 2160, level=0, supersample=2, nthreads=16, seed=0x504D5653)
 for cfg in cfgs:
