@@ -42,9 +42,11 @@
 
 namespace pmvsdev {
 
-// Neighbours per patch the walks hold in LDS.  The NB_CAP form runs every walk; the few patches
-// with more unique neighbours are walked again by the NB_CAP_BIG form (NbLdsT<16384>, about 130 KB
-// of LDS, one workgroup per CU); only beyond NB_CAP_BIG is the run an error.
+// Neighbours per patch the walks hold in LDS.  The NB_CAP form runs every walk.  The few patches
+// (neighbor_kernel) and candidates (depth_post_kernel) with more unique neighbours are walked again
+// by the NB_CAP_BIG form (NbLdsT<16384>, about 130 KB of LDS, one workgroup per CU); only beyond
+// NB_CAP_BIG is the run an error.  The parents empty_blocks_kernel overflows on are walked again by
+// empty_blocks_stream_kernel, which holds no neighbour list and so has no capacity.
 // PMVS_NB_CAP / PMVS_NB_GRID_MULT / PMVS_NB_WAVES_PER_EU: experiment variants only (tools/sweep_walks.sh,
 // `make variant VARTU=pmvs_filter`); the product builds the defaults.
 #ifndef PMVS_NB_CAP
@@ -57,7 +59,10 @@ constexpr int NB_CAP_BIG = PMVS_MAX_NEIGHBOURS;
 // (1.5 CAP).  Kept out of LDS so NbLds stays ~8 KB (occupancy of the latency-bound walks).
 constexpr int NB_SCR = NB_CAP * 8;
 constexpr int NB_GRID_BIG = 32;  // workgroups of the NB_CAP_BIG re-walks
-// gather_neighbors: cell slots per lane per round, entries per lane per test round
+// The neighbour walk: row slots per lane per round, entries per lane per test round.  A slot is one
+// ROW of a list's (2 margin + 1)^2 window: the row's cells are consecutive in the CSR cell order, so
+// their entries are the one range [off[c0], off[c0 + nx]) and a filterNeighbor walk loads 10 list
+// bounds per image, not 50.
 #ifndef PMVS_NB_SK  // experiment variants only (tools/sweep_walks.sh)
 #define PMVS_NB_SK 2
 #endif
@@ -66,13 +71,6 @@ constexpr int NB_GRID_BIG = 32;  // workgroups of the NB_CAP_BIG re-walks
 #endif
 constexpr int NB_SK = PMVS_NB_SK;
 constexpr int NB_NE = PMVS_NB_NE;
-// gather_neighbors' slots (round 6): 1 = one slot per ROW of a list's (2 margin + 1)^2 window -- the
-// row's cells are consecutive in the CSR cell order, so their entries are the one range
-// [off[c0], off[c0 + nx]) -- against 0 = one slot per cell (rounds 2-5).  The neighbour set is the
-// same; a filterNeighbor walk loads 10 list bounds per image instead of 50.
-#ifndef PMVS_NB_ROWS
-#define PMVS_NB_ROWS 1
-#endif
 // Diagnostic build only (-DNB_PROFILE, tools/r06w.sh): shader cycles per phase of the neighbour walks,
 // summed over wavefronts, per kernel (0 neighbor_kernel, 1 empty_blocks_kernel, 2 depth_post_kernel):
 // [0] setup (radius, units, seen-set clear), [1] slot bounds, [2] entries (items, tests, appends),
@@ -111,14 +109,24 @@ __device__ unsigned long long g_nb_prof[3][8];
 constexpr int NB_GRID_MULT = PMVS_NB_GRID_MULT;
 #ifdef PMVS_NB_WAVES_PER_EU
 #define NB_WALK_ATTR __attribute__((amdgpu_waves_per_eu(PMVS_NB_WAVES_PER_EU)))
+#define NB_STREAM_ATTR NB_WALK_ATTR
 #else
 #define NB_WALK_ATTR
+// empty_blocks_stream_kernel: without the hint the register allocator settles at 130 VGPRs, two past
+// 4 waves per SIMD; with it 122 and no scratch (make remarks VARTU=pmvs_filter)
+#define NB_STREAM_ATTR __attribute__((amdgpu_waves_per_eu(4)))
 #endif
 __device__ __forceinline__ int lane_id_w() { return threadIdx.x & 63; }
 // Wave-uniform copies (SGPR) of values that are uniform by construction but loaded from memory:
 // every branch or loop around a barrier is driven by one of these, never by a VGPR value.
 __device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
 __device__ __forceinline__ float uni_f(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
+// A persistent one-wavefront workgroup's next work-queue index: lane 0 draws it, every lane gets it (SGPR).
+__device__ __forceinline__ int next_ticket(int* queue) {
+  int i = 0;
+  if (threadIdx.x == 0) i = atomicAdd(queue, 1);
+  return __builtin_amdgcn_readfirstlane(i);
+}
 
 __host__ __device__ inline Reg reg_zero() {
   Reg r;
@@ -1168,9 +1176,6 @@ __device__ RadUnit compute_radius_unit(const DScene& s, NbSmall& L, const pmvs_p
   }
   return ru;
 }
-__device__ float compute_radius_wave(const DScene& s, NbSmall& L, const pmvs_patch& q) {
-  return compute_radius_unit(s, L, q, false).radius;
-}
 
 // CPatchOrganizerS::findNeighbors(patch, neighbors, lock, scale, margin, skipvis)
 // (patchOrganizerS.cpp:527-631) into L.nb[0..n), sorted by patch index and unique.  Returns n;
@@ -1229,13 +1234,134 @@ __device__ __forceinline__ void nb_append(NbLdsT<CAP>& L, bool hit, int j, int c
   if (cnt > cap - 64 && !uni(L.overflow)) sort_unique_lds(L.nb, imin(cnt, cap), &L.cnt);
 }
 
+// ---- The phases of findNeighbors' cell walk, shared by its two consumers: the buffered walk
+// (gather_neighbors: seen set, ballot append, compaction) and the bufferless re-walk
+// (empty_blocks_stream_kernel: test, then bin).  Each consumer calls them from its own round loop;
+// what it does with a candidate it meets stays with it.
+// One row slot of a round, slot = (list, row, pgrids / vpgrids), all zero when the slot is past the
+// end or its row lies outside the image's grid.
+struct NbSlot {
+  int bk = 0;        // the row's CSR list start; bit 31: vpgrids
+  int len = 0;       // its entries, over the row's cells
+  int hm = 0;        // bit dx: row cell dx has an expansion-time chain (FilterDev delta)
+  long long c0 = 0;  // the row's first cell
+};
+// The chain head of one cell (-1: no chain); only with expansion-time chains (F.pg_dhead != nullptr).
+__device__ __forceinline__ int nb_chain_head(const FilterDev& F, bool vp, long long cell) {
+  return (vp ? F.vp_dhead : F.pg_dhead)[cell];
+}
+// The slot decode, with the list's bound checks (F.err codes 12 pgrids, 13 vpgrids).
+__device__ __forceinline__ NbSlot nb_slot_decode(const DScene& s, const FilterDev& F, const pmvs_patch& q, int ni, int slot,
+                                                 int nslots, int margin) {
+  NbSlot sl;
+  if (slot >= nslots) return sl;
+  const int per_list = (2 * margin + 1) * 2;
+  const int li = slot / per_list;
+  const int r = slot - li * per_list;
+  const int dyi = r >> 1, lst = r & 1;
+  sl.bk = lst << 31;
+  const bool vis = li >= ni;
+  const int t = vis ? q.vimages[li - ni] : q.images[li];
+  if (t >= s.tnum) return sl;
+  const int gw = gwidth(s, t), gh = gheight(s, t);
+  const int yt = (vis ? q.vgrids[li - ni][1] : q.grids[li][1]) + dyi - margin;
+  const int gx = vis ? q.vgrids[li - ni][0] : q.grids[li][0];
+  const int x0 = imax(gx - margin, 0), x1 = imin(gx + margin, gw - 1);
+  if (!(0 <= yt && yt < gh && x0 <= x1)) return sl;
+  sl.c0 = F.tgoff[t] + (long long)yt * gw + x0;
+  const int nx = x1 - x0 + 1;
+  const int* off = lst ? F.vp_off : F.pg_off;
+  int b = off[sl.c0], e = off[sl.c0 + nx];
+  if (b < 0 || e > (lst ? F.nvp : F.npg) || b > e) {
+    atomicAdd(&F.err[0], 1);
+    atomicExch(&F.err[1], 12 + lst);
+    b = 0;
+    e = 0;
+  }
+  sl.bk |= b;
+  sl.len = e - b;
+  if (F.pg_dhead != nullptr)
+    for (int dx = 0; dx < nx; ++dx) sl.hm |= (nb_chain_head(F, lst, sl.c0 + dx) >= 0 ? 1 : 0) << dx;
+  return sl;
+}
+// The round's scan: its CSR entries flattened in (lane, k) order, each slot's list start published in
+// L.sb and its flat offset in L.so.  Returns their number (wave-uniform).
+__device__ __forceinline__ int nb_round_publish(NbSmall& L, const NbSlot (&sl)[NB_SK]) {
+  const int lane = lane_id_w();
+  int mine = 0;
+#pragma unroll
+  for (int k = 0; k < NB_SK; ++k) mine += sl[k].len;
+  int o = wave_excl_scan_w(mine);
+  const int tot = uni(__shfl(o + mine, 63));
+#pragma unroll
+  for (int k = 0; k < NB_SK; ++k) {
+    L.sb[lane * NB_SK + k] = sl[k].bk;
+    L.so[lane * NB_SK + k] = o;
+    o += sl[k].len;
+  }
+  __syncthreads();
+  return tot;
+}
+// The round's flat entries ib + u * 64 + lane, u < NB_NE, as items: the slot that holds the entry by
+// binary search over L.so, the item loads issued together.  Entry u exists when ib + u * 64 + lane <
+// tot; the consumer range-checks it with nb_item_ok (F.err code 14) as it comes to it.
+__device__ __forceinline__ void nb_fetch_items(const FilterDev& F, const NbSmall& L, int ib, int tot, int (&jv)[NB_NE]) {
+  const int lane = lane_id_w();
+#pragma unroll
+  for (int u = 0; u < NB_NE; ++u) {
+    const int idx = ib + u * 64 + lane;
+    jv[u] = -1;
+    if (idx < tot) {
+      int sidx = 0;  // the last slot whose offset is <= idx (it holds idx)
+      for (int step = 64 * NB_SK / 2; step >= 1; step >>= 1)
+        if (sidx + step < 64 * NB_SK && L.so[sidx + step] <= idx) sidx += step;
+      const int sb = L.sb[sidx];
+      const int* items = (sb < 0) ? F.vp_items : F.pg_items;
+      jv[u] = items[(sb & 0x7fffffff) + idx - L.so[sidx]];
+    }
+  }
+}
+// The range check of a met item, an F.err of `code` (14 CSR entry, 15 chain entry) when it fails.
+__device__ __forceinline__ bool nb_item_ok(const FilterDev& F, bool met, int j, int code) {
+  if (!met) return false;
+  if (j < 0 || j >= F.n) {
+    atomicAdd(&F.err[0], 1);
+    atomicExch(&F.err[1], code);
+    return false;
+  }
+  return true;
+}
+// Entries committed by earlier expansion waves (per-cell chains): one cursor per cell dx0 + m, m < MC,
+// of the slot's row (-1 where the cell has no chain or lies past the row's `side` cells), and one step
+// of every live cursor -- their entry loads in flight together, so a step costs one dependent load,
+// not one per cell.  jm[m] = -2: cursor m was idle; the consumer range-checks the others with
+// nb_item_ok (F.err code 15).
+template <int MC>
+__device__ __forceinline__ void nb_chain_heads(const FilterDev& F, const NbSlot& sl, int dx0, int side, int (&cur)[MC]) {
+#pragma unroll
+  for (int m = 0; m < MC; ++m)
+    cur[m] = (dx0 + m < side && ((sl.hm >> (dx0 + m)) & 1)) ? nb_chain_head(F, sl.bk < 0, sl.c0 + dx0 + m) : -1;
+}
+template <int MC>
+__device__ __forceinline__ void nb_chain_step(const FilterDev& F, int (&cur)[MC], int (&jm)[MC]) {
+#pragma unroll
+  for (int m = 0; m < MC; ++m) {
+    jm[m] = -2;
+    if (cur[m] >= 0) {
+      const int2 en = F.d_ent[cur[m]];
+      jm[m] = en.x;
+      cur[m] = en.y;
+    }
+  }
+}
+
 // CPatchOrganizerS::findNeighbors(patch, neighbors, lock, scale, margin, skipvis)
 // (patchOrganizerS.cpp:527-631) into L.nb[0..n), sorted by patch index and unique.  Returns n;
 // L.overflow is set when more than NB_CAP unique neighbours exist.
-// The (image list, dy, dx, pgrids/vpgrids) cells are visited 64 at a time, one per lane (their
-// list bounds load in parallel); the cells' entries are then flattened and tested 64 per round.
-// Expansion-time chain entries (FilterDev delta) are walked per lane.  The neighbour SET is the
-// reference's; the visiting order only matters for the buffer's compaction points.
+// The buffered consumer of the phases above: the (image list, dy, pgrids/vpgrids) row slots 64 NB_SK
+// per round (their list bounds load in parallel), their entries flattened and tested 64 NB_NE at a
+// time, each patch once (seen set); expansion-time chains (FilterDev delta) one cursor per row cell.
+// The neighbour SET is the reference's; the visiting order only matters for the compaction points.
 // CHM: the largest margin whose expansion-time chains the caller walks (0: the filter pass, which has
 // none -- F.pg_dhead is nullptr there; chains met anyway are an error, code 16).
 template <int CAP, int CHM>
@@ -1258,120 +1384,29 @@ __device__ __forceinline__ int gather_neighbors(const DScene& s, const FilterDev
   __syncthreads();
   const int nlists = skipvis ? ni : ni + uni(q.num_vimages);
   const int side = 2 * margin + 1;
-#if PMVS_NB_ROWS
-  const int per_list = side * 2;  // (row, pgrids / vpgrids)
-#else
-  const int per_list = side * side * 2;  // (row, column, pgrids / vpgrids)
-#endif
   const bool chains = F.pg_dhead != nullptr;
-  const int nslots = nlists * per_list;
+  const int nslots = nlists * side * 2;  // (list, row, pgrids / vpgrids)
   // NB_SK slots per lane per round (their list bounds load together), then the round's entries
   // NB_NE per lane at a time (their item and patch loads in flight together): fewer dependent
   // global-memory round trips per patch than one slot / one entry per lane.
   for (int base = 0; base < nslots; base += 64 * NB_SK) {
-    // per slot: list start (bit 31: vpgrids) and length; for the expansion's chains its first cell
-    // and the cells (bit dx) whose chain is not empty
-    int bk[NB_SK], ck[NB_SK], hk[NB_SK];
-    long long ck0[NB_SK];
-#pragma unroll
+    NbSlot sl[NB_SK];
     NBP(base == 0 ? 0 : 2);
-    for (int k = 0; k < NB_SK; ++k) {
-      const int slot = base + k * 64 + lane;
-      int b = 0, e = 0, lst = 0, hm = 0;
-      long long c0 = 0;
-      if (slot < nslots) {
-        const int li = slot / per_list;
-        int r = slot - li * per_list;
-#if PMVS_NB_ROWS
-        const int dyi = r >> 1;
-        lst = r & 1;
-#else
-        const int dyi = r / (2 * side);
-        r -= dyi * 2 * side;
-        const int dxi = r >> 1;
-        lst = r & 1;
-#endif
-        const bool vis = li >= ni;
-        const int t = vis ? q.vimages[li - ni] : q.images[li];
-        if (t < s.tnum) {
-          const int gw = gwidth(s, t), gh = gheight(s, t);
-          const int yt = (vis ? q.vgrids[li - ni][1] : q.grids[li][1]) + dyi - margin;
-          const int gx = vis ? q.vgrids[li - ni][0] : q.grids[li][0];
-#if PMVS_NB_ROWS
-          const int x0 = imax(gx - margin, 0), x1 = imin(gx + margin, gw - 1);
-#else
-          const int x0 = gx + dxi - margin, x1 = x0;
-#endif
-          if (0 <= yt && yt < gh && 0 <= x0 && x0 <= x1 && x1 < gw) {
-            c0 = F.tgoff[t] + (long long)yt * gw + x0;
-            const int nx = x1 - x0 + 1;
-            const int* off = lst ? F.vp_off : F.pg_off;
-            const int lim = lst ? F.nvp : F.npg;
-            b = off[c0];
-            e = off[c0 + nx];
-            if (b < 0 || e > lim || b > e) {
-              atomicAdd(&F.err[0], 1);
-              atomicExch(&F.err[1], 12 + lst);
-              b = 0;
-              e = 0;
-            }
-            if (chains) {
-              const int* dh = lst ? F.vp_dhead : F.pg_dhead;
-              for (int dx = 0; dx < nx; ++dx) hm |= (dh[c0 + dx] >= 0 ? 1 : 0) << dx;
-            }
-          }
-        }
-      }
-      bk[k] = b | (lst << 31);  // list start, list kind in bit 31
-      ck[k] = e - b;
-      hk[k] = hm;
-      ck0[k] = c0;
-    }
-    // the round's CSR entries, flattened in (lane, k) order
-    int mine = 0;
 #pragma unroll
-    for (int k = 0; k < NB_SK; ++k) mine += ck[k];
-    const int offl = wave_excl_scan_w(mine);
-    const int tot = uni(__shfl(offl + mine, 63));
-    {
-      int o = offl;
-#pragma unroll
-      for (int k = 0; k < NB_SK; ++k) {
-        L.sb[lane * NB_SK + k] = bk[k];
-        L.so[lane * NB_SK + k] = o;
-        o += ck[k];
-      }
-    }
-    __syncthreads();
+    for (int k = 0; k < NB_SK; ++k) sl[k] = nb_slot_decode(s, F, q, ni, base + k * 64 + lane, nslots, margin);
+    const int tot = nb_round_publish(L, sl);
     NBP(1);
     for (int ib = 0; ib < tot; ib += 64 * NB_NE) {
       int jv[NB_NE];
       bool hv[NB_NE];
-#pragma unroll
-      for (int u = 0; u < NB_NE; ++u) {
-        const int idx = ib + u * 64 + lane;
-        jv[u] = -1;
-        if (idx < tot) {
-          int sidx = 0;  // the last slot whose offset is <= idx (it holds idx)
-          for (int step = 64 * NB_SK / 2; step >= 1; step >>= 1)
-            if (sidx + step < 64 * NB_SK && L.so[sidx + step] <= idx) sidx += step;
-          const int sb = L.sb[sidx];
-          const int* items = (sb < 0) ? F.vp_items : F.pg_items;
-          jv[u] = items[(sb & 0x7fffffff) + idx - L.so[sidx]];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < NB_NE; ++u) {
-        const int j = jv[u];
-        hv[u] = false;
-        if (ib + u * 64 + lane < tot) {
-          if (j < 0 || j >= F.n) { atomicAdd(&F.err[0], 1); atomicExch(&F.err[1], 14); jv[u] = 0; }
-          else if (nb_first_visit(L, j)) hv[u] = is_neighbor_h(q, F.hot[j], unit, thr, radius, true) != 0;
-        }
-      }
+      nb_fetch_items(F, L, ib, tot, jv);
 #pragma unroll
       for (int u = 0; u < NB_NE; ++u)
-        if (ib + u * 64 < tot) nb_append(L, hv[u], jv[u] < 0 ? 0 : jv[u], cap);
+        hv[u] = nb_item_ok(F, ib + u * 64 + lane < tot, jv[u], 14) && nb_first_visit(L, jv[u]) &&
+                is_neighbor_h(q, F.hot[jv[u]], unit, thr, radius, true) != 0;
+#pragma unroll
+      for (int u = 0; u < NB_NE; ++u)
+        if (ib + u * 64 < tot) nb_append(L, hv[u], jv[u], cap);
     }
     NBP(2);
     // entries committed by earlier expansion waves (per-cell chains, FilterDev delta): slot by slot,
@@ -1381,7 +1416,7 @@ __device__ __forceinline__ int gather_neighbors(const DScene& s, const FilterDev
     // growing model is in chains, spent 69 % of findEmptyBlocks' cycles here cell by cell, r06w)
     int hany = 0;
 #pragma unroll
-    for (int k = 0; k < NB_SK; ++k) hany |= hk[k];
+    for (int k = 0; k < NB_SK; ++k) hany |= sl[k].hm;
     if (chains && __ballot(hany != 0) != 0ull) {
       if (CHM == 0 || margin > CHM) {
         if (lane == 0) { atomicAdd(&F.err[0], 1); atomicExch(&F.err[1], 16); }
@@ -1389,45 +1424,31 @@ __device__ __forceinline__ int gather_neighbors(const DScene& s, const FilterDev
         constexpr int MC = 2 * CHM + 1;
 #pragma unroll
         for (int k = 0; k < NB_SK; ++k) {
-        if (__ballot(hk[k] != 0) == 0ull) continue;
-        int cur[MC];
+          if (__ballot(sl[k].hm != 0) == 0ull) continue;
+          int cur[MC];
+          nb_chain_heads(F, sl[k], 0, side, cur);
+          for (;;) {
+            int adds = 0;  // the round's appends at most: its live cursors over the wavefront
 #pragma unroll
-        for (int dx = 0; dx < MC; ++dx) {
-          const int* dh = (bk[k] < 0) ? F.vp_dhead : F.pg_dhead;
-          cur[dx] = (dx < side && ((hk[k] >> dx) & 1)) ? dh[ck0[k] + dx] : -1;
-        }
-        for (;;) {
-          int adds = 0;  // the round's appends at most: its live cursors over the wavefront
+            for (int m = 0; m < MC; ++m) adds += __popcll(__ballot(cur[m] >= 0));
+            if (adds == 0) break;
+            const int cnt0 = uni(L.cnt);
+            if (cnt0 + adds > cap && !uni(L.overflow)) sort_unique_lds(L.nb, imin(cnt0, cap), &L.cnt);
+            int jm[MC];
+            nb_chain_step(F, cur, jm);
 #pragma unroll
-          for (int m = 0; m < MC; ++m) adds += __popcll(__ballot(cur[m] >= 0));
-          if (adds == 0) break;
-          const int cnt0 = uni(L.cnt);
-          if (cnt0 + adds > cap && !uni(L.overflow)) sort_unique_lds(L.nb, imin(cnt0, cap), &L.cnt);
-          int jm[MC];
-#pragma unroll
-          for (int m = 0; m < MC; ++m) {
-            jm[m] = -2;
-            if (cur[m] >= 0) {
-              const int2 en = F.d_ent[cur[m]];
-              jm[m] = en.x;
-              cur[m] = en.y;
+            for (int m = 0; m < MC; ++m) {
+              const int j = jm[m];
+              if (nb_item_ok(F, j != -2, j, 15) && nb_first_visit(L, j) && is_neighbor_h(q, F.hot[j], unit, thr, radius, true)) {
+                const int pos = atomicAdd(&L.cnt, 1);
+                if (pos < cap) L.nb[pos] = j;
+                else L.overflow = 1;
+              }
             }
+            __syncthreads();
+            if (lane == 0 && L.cnt > cap) L.cnt = cap;
+            __syncthreads();
           }
-#pragma unroll
-          for (int m = 0; m < MC; ++m) {
-            const int j = jm[m];
-            if (j == -2) continue;
-            if (j < 0 || j >= F.n) { atomicAdd(&F.err[0], 1); atomicExch(&F.err[1], 15); continue; }
-            if (nb_first_visit(L, j) && is_neighbor_h(q, F.hot[j], unit, thr, radius, true)) {
-              const int pos = atomicAdd(&L.cnt, 1);
-              if (pos < cap) L.nb[pos] = j;
-              else L.overflow = 1;
-            }
-          }
-          __syncthreads();
-          if (lane == 0 && L.cnt > cap) L.cnt = cap;
-          __syncthreads();
-        }
         }
         const int cnt = uni(L.cnt);
         if (cnt > cap - 64 && !uni(L.overflow)) sort_unique_lds(L.nb, imin(cnt, cap), &L.cnt);
@@ -1436,14 +1457,22 @@ __device__ __forceinline__ int gather_neighbors(const DScene& s, const FilterDev
     __syncthreads();
     NBP(3);
   }
-  const int n = imin(uni(L.cnt), cap);
-#if defined(NBX_SKIP_SORT)  // timing experiment only (tools): the final sort skipped
-  return n;
-#else
-  const int nu = sort_unique_lds(L.nb, n, &L.cnt);
+  const int nu = sort_unique_lds(L.nb, imin(uni(L.cnt), cap), &L.cnt);
   NBP(4);
   return nu;
-#endif
+}
+
+// The patch's tangent frame from its normal (filter.cpp:393-404, expand.cpp:113-124): xdir along the
+// normal's dominant pair of axes, unitized, ydir = normal x xdir.
+__device__ __forceinline__ void patch_frame(const float* z, float (&xdir)[4], float (&ydir)[4]) {
+  for (int c = 0; c < 4; ++c) xdir[c] = ydir[c] = 0;
+  if (fabs((double)z[0]) > 0.5) { xdir[0] = z[1]; xdir[1] = -z[0]; xdir[2] = 0; }
+  else if (fabs((double)z[1]) > 0.5) { xdir[1] = z[2]; xdir[2] = -z[1]; xdir[0] = 0; }
+  else { xdir[2] = z[0]; xdir[0] = -z[2]; xdir[1] = 0; }
+  unitize4(xdir);
+  ydir[0] = z[1] * xdir[2] - z[2] * xdir[1];
+  ydir[1] = z[2] * xdir[0] - z[0] * xdir[2];
+  ydir[2] = z[0] * xdir[1] - z[1] * xdir[0];
 }
 
 // CFilter::filterQuad (filter.cpp:387-446) on the neighbours in L.nb[0..n); returns 1 = reject.
@@ -1454,15 +1483,8 @@ __device__ __forceinline__ int filter_quad_wave(const DScene& s, const FilterDev
                                 const pmvs_patch& q, int n, float* fout = nullptr) {
   const int lane = lane_id_w();
   n = uni(n);
-  float xdir[4] = {0, 0, 0, 0}, ydir[4] = {0, 0, 0, 0};
-  const float* z = q.normal;
-  if (fabs((double)z[0]) > 0.5) { xdir[0] = z[1]; xdir[1] = -z[0]; xdir[2] = 0; }
-  else if (fabs((double)z[1]) > 0.5) { xdir[1] = z[2]; xdir[2] = -z[1]; xdir[0] = 0; }
-  else { xdir[2] = z[0]; xdir[0] = -z[2]; xdir[1] = 0; }
-  unitize4(xdir);
-  ydir[0] = z[1] * xdir[2] - z[2] * xdir[1];
-  ydir[1] = z[2] * xdir[0] - z[0] * xdir[2];
-  ydir[2] = z[0] * xdir[1] - z[1] * xdir[0];
+  float xdir[4], ydir[4];
+  patch_frame(q.normal, xdir, ydir);
   float* gx = fout ? fout : reinterpret_cast<float*>(r + CAP);  // fx, fy, fz (workgroup's global scratch)
   float* gy = gx + (fout ? n : CAP);
   float* gz = gy + (fout ? n : CAP);
@@ -1504,12 +1526,7 @@ __device__ __forceinline__ int filter_quad_wave(const DScene& s, const FilterDev
   }
   __threadfence_block();
   __syncthreads();
-#if defined(NBX_SKIP_LLS)  // timing experiment only (tools): the quadric fit skipped
-  if (lane < 5) L.x[lane] = 0.0f;
-  __syncthreads();
-#else
   lls5_wave(L, M, r, n);
-#endif
   // The residual terms |r_a| / u2 in parallel (each lane its own rows; every lane computes the same
   // u2), into the lls rows' space (free now), then their float += double sum in the reference's order.
   const int inum = imin(s.tau, q.num_images);
@@ -1540,13 +1557,15 @@ __device__ __forceinline__ int filter_quad_wave(const DScene& s, const FilterDev
 // Sharded loop (world > 1): a rank tests only the patches whose reference image it owns
 // (target t belongs to rank t mod world); the others are left to their owners
 // and the reject flags are all-gathered afterwards (filter_pass).
-// Overflow (more than CAP unique neighbours): with `ovf` (the NB_CAP form) the patch goes on the
-// re-walk list ovf.items and the NB_CAP_BIG form (ovf.only: walks that list) decides it; without,
-// it is counted in `overflow` (an error for the run).
+// Overflow (more than CAP unique neighbours): the NB_CAP form (ov.items set) puts the patch on the
+// re-walk list ov.items and the NB_CAP_BIG form (ov.only: walks that list) decides it; there it is
+// counted in `overflow` (an error for the run).  depth_post_kernel does the same with its candidates.
+// empty_blocks_kernel's overflowed parents are re-walked by empty_blocks_stream_kernel, which has
+// no capacity and so no error.
 struct NbOverflow {
-  int* items = nullptr;        // NB_CAP form: the overflowed work items (patch / parent / candidate)
+  int* items = nullptr;        // the NB_CAP walk: the overflowed work items (patch / parent / candidate)
   int* count = nullptr;        // their number
-  const int* only = nullptr;   // NB_CAP_BIG form: walk items only[0 .. *only_n)
+  const int* only = nullptr;   // the re-walk (NB_CAP_BIG or stream form): walk items only[0 .. *only_n)
   const int* only_n = nullptr;
 };
 template <int CAP>
@@ -1565,9 +1584,7 @@ __global__ __launch_bounds__(64) NB_WALK_ATTR void neighbor_kernel(DScene s, Fil
 #endif
   for (;;) {
     NBP(6);
-    int i = 0;
-    if (lane == 0) i = atomicAdd(queue, 1);
-    i = __builtin_amdgcn_readfirstlane(i);  // work-queue index, wave-uniform (SGPR)
+    const int i = next_ticket(queue);
     if (i >= (ov.only ? *ov.only_n : F.nalive)) break;
     const int p = __builtin_amdgcn_readfirstlane(ov.only ? ov.only[i] : F.order[i]);
     const pmvs_patch& q = F.P[p];
@@ -2132,109 +2149,10 @@ __global__ void group_edges_kernel(DScene s, FilterDev F, int pass, const int* _
 // CExpand::findEmptyBlocks (expand.cpp:95-180), one wavefront per parent: the six angular
 // bins around the patch that hold no neighbour (findNeighbors(patch, ., 1, 4.0f), margin 1,
 // vimages included) and were not tried before (_dflag) get a candidate at `radius`.
-template <int CAP>
-__global__ __launch_bounds__(64) NB_WALK_ATTR void empty_blocks_kernel(DScene s, FilterDev F, const int* __restrict__ parents, int np,
-                                                          float* __restrict__ cand_coord, int* __restrict__ cand_ok,
-                                                          int* __restrict__ queue, int* __restrict__ overflow, NbOverflow ov) {
-  __shared__ NbLdsT<CAP> L;
-  const int lane = threadIdx.x;
-#if defined(NB_PROFILE)
-  unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0}, nbp_t = NBP_NOW();
-#else
-  unsigned long long* prof = nullptr;
-#endif
-  for (;;) {
-    NBP(5);
-    int i = 0;
-    if (lane == 0) i = atomicAdd(queue, 1);
-    i = __builtin_amdgcn_readfirstlane(i);
-    if (i >= (ov.only ? *ov.only_n : np)) break;
-    const int k = ov.only ? __builtin_amdgcn_readfirstlane(ov.only[i]) : i;
-    const pmvs_patch& q = F.P[parents[k]];
-    const RadUnit ru = compute_radius_unit(s, L, q, true);
-    const float radius = ru.radius;
-    NBP(6);
-#if defined(EBX_SKIP_WALK)  // timing experiment only (tools/eb_breakdown.sh): no neighbour walk
-    const int n = 0;
-    if (lane == 0) L.overflow = 0;
-#else
-    const int n = gather_neighbors<CAP, 1>(s, F, L, q, 4.0f, 1, 0, prof, ru);  // the radius and units computed once
-#endif
-#if defined(NB_PROFILE)
-    nbp_t = NBP_NOW();
-#endif
-    // overflowed: this parent's bins are rewritten by the NB_CAP_BIG re-walk
-    if (lane == 0 && L.overflow && ov.items) ov.items[atomicAdd(ov.count, 1)] = k;
-    if (lane == 0 && L.overflow && !ov.items) atomicAdd(overflow, 1);
-    float xdir[4] = {0, 0, 0, 0}, ydir[4] = {0, 0, 0, 0};
-    const float* z = q.normal;
-    if (fabs((double)z[0]) > 0.5) { xdir[0] = z[1]; xdir[1] = -z[0]; xdir[2] = 0; }
-    else if (fabs((double)z[1]) > 0.5) { xdir[1] = z[2]; xdir[2] = -z[1]; xdir[0] = 0; }
-    else { xdir[2] = z[0]; xdir[0] = -z[2]; xdir[1] = 0; }
-    unitize4(xdir);
-    ydir[0] = z[1] * xdir[2] - z[2] * xdir[1];
-    ydir[1] = z[2] * xdir[0] - z[0] * xdir[2];
-    ydir[2] = z[0] * xdir[1] - z[1] * xdir[0];
-    const float radiuslow = __fdiv_rn(radius, 6.0f), radiushigh = radius * 2.5f;
-    // fill[i] of the reference is a sum of non-negative terms compared with 0 (expand.cpp:160-176):
-    // it is > 0 iff some term is > 0 and none is NaN, so the neighbours are scanned lane-parallel
-    // and only those two facts per bin are reduced.
-    unsigned pos = 0u, nan = 0u;
-#if defined(EBX_SKIP_BIN)  // timing experiment only (tools/eb_breakdown.sh): the neighbours not binned
-    for (int a = lane; a < 0; a += 64) {
-#else
-    for (int a = lane; a < n; a += 64) {
-#endif
-      float d[4];
-      for (int c = 0; c < 4; ++c) d[c] = F.hot[L.nb[a]].coord[c] - q.coord[c];
-      float f0 = dot4(d, xdir), f1 = dot4(d, ydir);
-      const float len = (float)sqrt((double)(f0 * f0 + f1 * f1));
-      if (len < radiuslow || radiushigh < len) continue;
-      f0 = __fdiv_rn(f0, len);
-      f1 = __fdiv_rn(f1, len);
-      float angle = (float)atan2((double)f1, (double)f0);
-      if (angle < 0.0) angle = (float)((double)angle + 2 * M_PI);
-      const float findex = (float)((double)angle / (2 * M_PI / 6));
-      const int lindex = (int)floor((double)findex);
-      const int hindex = lindex + 1;
-      const float t0 = (float)hindex - findex, t1 = findex - (float)lindex;
-      const int b0 = ((lindex % 6) + 6) % 6, b1 = ((hindex % 6) + 6) % 6;
-      if (t0 > 0.0f) pos |= 1u << b0;
-      if (t0 != t0) nan |= 1u << b0;
-      if (t1 > 0.0f) pos |= 1u << b1;
-      if (t1 != t1) nan |= 1u << b1;
-    }
-    for (int d = 32; d >= 1; d >>= 1) {
-      pos |= __shfl_xor(pos, d);
-      nan |= __shfl_xor(nan, d);
-    }
-    if (lane == 0) {
-      for (int i = 0; i < 6; ++i) {
-        int ok = 1;
-        if ((pos >> i & 1u) && !(nan >> i & 1u)) ok = 0;  // 0.0f < fill[i]
-        if (q.dflag & (0x0001 << i)) ok = 0;
-        cand_ok[6 * k + i] = ok;
-        if (ok) {
-          // expand.cpp:176-177: the angle is stored as float, then cos/sin run in double.
-          const float angle = (float)(2 * M_PI * i / 6);
-          const double cr = cos((double)angle) * (double)radius, sr = sin((double)angle) * (double)radius;
-          for (int c = 0; c < 4; ++c)
-            cand_coord[4 * (6 * k + i) + c] = (q.coord[c] + (float)((double)xdir[c] * cr)) + (float)((double)ydir[c] * sr);
-        }
-      }
-    }
-    __syncthreads();
-  }
-  NBP_FLUSH(1);
-}
-
-// findEmptyBlocks' re-walk of the parents whose neighbour set overflowed the NB_CAP walk (round 5:
-// replaces the NB_CAP_BIG form, whose 16 384-entry LDS buffer could overflow in its turn on dense
-// 8K clusters).  fill[] of the reference (expand.cpp:160-176) only needs, per angular bin, whether
-// some term is > 0 and whether one is NaN; neither depends on the order of the neighbour list or on
-// duplicates in it, so this walk bins each neighbour as it meets it: no buffer, no sort, no
-// capacity.  As the only walk it measured 10 % slower (duplicates re-tested, 146 registers, branch
-// exp-stream-walks); as the re-walk of a few parents its speed does not matter.
+// fill[i] of the reference is a sum of non-negative terms compared with 0 (expand.cpp:160-176): it
+// is > 0 iff some term is > 0 and none is NaN, so the neighbours are binned lane-parallel (eb_bin:
+// one neighbour's two bins into the lane's pos / nan bit sets) and only those two facts per bin are
+// reduced over the wavefront (eb_write_candidates).
 __device__ __forceinline__ void eb_bin(const float* hc, const float* qc, const float* xdir, const float* ydir, float rlow,
                                        float rhigh, unsigned& pos, unsigned& nan) {
   float d[4];
@@ -2257,153 +2175,133 @@ __device__ __forceinline__ void eb_bin(const float* hc, const float* qc, const f
   if (t1 != t1) nan |= 1u << b1;
 }
 
-__global__ __launch_bounds__(64) NB_WALK_ATTR void empty_blocks_stream_kernel(DScene s, FilterDev F, const int* __restrict__ parents,
+// The six directions of parent slot k from the lanes' bins: cand_ok[6 k + i] = bin i holds no
+// neighbour and was not tried before (dflag), and for those the candidate at `radius` in the frame.
+__device__ __forceinline__ void eb_write_candidates(unsigned pos, unsigned nan, const pmvs_patch& q, float radius,
+                                                    const float (&xdir)[4], const float (&ydir)[4], int k,
+                                                    float* __restrict__ cand_coord, int* __restrict__ cand_ok) {
+  for (int d = 32; d >= 1; d >>= 1) {
+    pos |= __shfl_xor(pos, d);
+    nan |= __shfl_xor(nan, d);
+  }
+  if (threadIdx.x != 0) return;
+  for (int i = 0; i < 6; ++i) {
+    int ok = 1;
+    if ((pos >> i & 1u) && !(nan >> i & 1u)) ok = 0;  // 0.0f < fill[i]
+    if (q.dflag & (0x0001 << i)) ok = 0;
+    cand_ok[6 * k + i] = ok;
+    if (ok) {
+      // expand.cpp:176-177: the angle is stored as float, then cos/sin run in double.
+      const float angle = (float)(2 * M_PI * i / 6);
+      const double cr = cos((double)angle) * (double)radius, sr = sin((double)angle) * (double)radius;
+      for (int c = 0; c < 4; ++c)
+        cand_coord[4 * (6 * k + i) + c] = (q.coord[c] + (float)((double)xdir[c] * cr)) + (float)((double)ydir[c] * sr);
+    }
+  }
+}
+
+// The NB_CAP walk of every parent: the neighbours into L.nb, then binned.  A parent with more than
+// NB_CAP neighbours goes on the re-walk list ov.items; empty_blocks_stream_kernel rewrites its bins.
+template <int CAP>
+__global__ __launch_bounds__(64) NB_WALK_ATTR void empty_blocks_kernel(DScene s, FilterDev F, const int* __restrict__ parents, int np,
+                                                          float* __restrict__ cand_coord, int* __restrict__ cand_ok,
+                                                          int* __restrict__ queue, NbOverflow ov) {
+  __shared__ NbLdsT<CAP> L;
+  const int lane = threadIdx.x;
+#if defined(NB_PROFILE)
+  unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0}, nbp_t = NBP_NOW();
+#else
+  unsigned long long* prof = nullptr;
+#endif
+  for (;;) {
+    NBP(5);
+    const int k = next_ticket(queue);
+    if (k >= np) break;
+    const pmvs_patch& q = F.P[parents[k]];
+    const RadUnit ru = compute_radius_unit(s, L, q, true);
+    const float radius = ru.radius;
+    NBP(6);
+    const int n = gather_neighbors<CAP, 1>(s, F, L, q, 4.0f, 1, 0, prof, ru);  // the radius and units computed once
+#if defined(NB_PROFILE)
+    nbp_t = NBP_NOW();
+#endif
+    if (lane == 0 && L.overflow) ov.items[atomicAdd(ov.count, 1)] = k;
+    float xdir[4], ydir[4];
+    patch_frame(q.normal, xdir, ydir);
+    const float radiuslow = __fdiv_rn(radius, 6.0f), radiushigh = radius * 2.5f;
+    unsigned pos = 0u, nan = 0u;
+    for (int a = lane; a < n; a += 64) eb_bin(F.hot[L.nb[a]].coord, q.coord, xdir, ydir, radiuslow, radiushigh, pos, nan);
+    eb_write_candidates(pos, nan, q, radius, xdir, ydir, k, cand_coord, cand_ok);
+    __syncthreads();
+  }
+  NBP_FLUSH(1);
+}
+
+// findEmptyBlocks' re-walk of the parents whose neighbour set overflowed the NB_CAP walk (round 5:
+// replaces the NB_CAP_BIG form, whose 16 384-entry LDS buffer could overflow in its turn on dense
+// 8K clusters).  Neither of the two facts per bin depends on the order of the neighbour list or on
+// duplicates in it, so this walk bins each neighbour as it meets it: no seen set, no buffer, no
+// sort, no capacity.  As the only walk it measured 10 % slower (duplicates re-tested, 146 registers,
+// branch exp-stream-walks); as the re-walk of a few parents its speed does not matter.
+__global__ __launch_bounds__(64) NB_STREAM_ATTR void empty_blocks_stream_kernel(DScene s, FilterDev F, const int* __restrict__ parents,
                                                                               float* __restrict__ cand_coord, int* __restrict__ cand_ok,
                                                                               int* __restrict__ queue, NbOverflow ov) {
   __shared__ NbSmall L;
   const int lane = threadIdx.x;
-  constexpr int margin = 1;
+  constexpr int margin = 1, side = 2 * margin + 1;
   for (;;) {
-    int i = 0;
-    if (lane == 0) i = atomicAdd(queue, 1);
-    i = __builtin_amdgcn_readfirstlane(i);
+    const int i = next_ticket(queue);
     if (i >= *ov.only_n) break;
     const int pk = __builtin_amdgcn_readfirstlane(ov.only[i]);  // an overflowed parent of the NB_CAP walk
     const pmvs_patch& q = F.P[parents[pk]];
-    const float radius = compute_radius_wave(s, L, q);
-    float xdir[4] = {0, 0, 0, 0}, ydir[4] = {0, 0, 0, 0};
-    const float* z = q.normal;
-    if (fabs((double)z[0]) > 0.5) { xdir[0] = z[1]; xdir[1] = -z[0]; xdir[2] = 0; }
-    else if (fabs((double)z[1]) > 0.5) { xdir[1] = z[2]; xdir[2] = -z[1]; xdir[0] = 0; }
-    else { xdir[2] = z[0]; xdir[0] = -z[2]; xdir[1] = 0; }
-    unitize4(xdir);
-    ydir[0] = z[1] * xdir[2] - z[2] * xdir[1];
-    ydir[1] = z[2] * xdir[0] - z[0] * xdir[2];
-    ydir[2] = z[0] * xdir[1] - z[1] * xdir[0];
-    const float radiuslow = __fdiv_rn(radius, 6.0f), radiushigh = radius * 2.5f;
-    // findNeighbors(patch, ., 1, 4.0f) (patchOrganizerS.cpp:527-631) as in gather_neighbors: the
-    // cells NB_SK per lane per round, their entries NB_NE per lane at a time
+    const RadUnit ru = compute_radius_unit(s, L, q, true);
+    const float radius = uni_f(ru.radius);
+    float xdir[4], ydir[4];
+    patch_frame(q.normal, xdir, ydir);
+    // every lane holds the same per-parent values: kept in SGPRs (the walk with the binning inlined
+    // at each meeting is at the 128-VGPR edge of 4 waves per SIMD)
+    for (int c = 0; c < 3; ++c) { xdir[c] = uni_f(xdir[c]); ydir[c] = uni_f(ydir[c]); }
+    const float radiuslow = uni_f(__fdiv_rn(radius, 6.0f)), radiushigh = uni_f(radius * 2.5f);
+    // findNeighbors(patch, ., 1, 4.0f) (patchOrganizerS.cpp:527-631) with gather_neighbors' rounds
     const int ni = uni(q.num_images);
-    const float nradius = (float)(1.5 * margin * (double)radius);
-    float unit = 0.0f;
-    for (int k = 0; k < ni; ++k) unit += get_unit(s, s.views[q.images[k]], q.coord);
-    unit = __fdiv_rn(unit, (float)ni);
-    unit *= (float)s.csize;
+    const float nradius = uni_f((float)(1.5 * margin * (double)radius));
+    float unit = __fdiv_rn(ru.usum, (float)ni);
+    unit = uni_f(unit * (float)s.csize);
     const float thr = 0.5f * 4.0f;
-    const int nlists = ni + uni(q.num_vimages);
-    constexpr int side = 2 * margin + 1, per_list = side * side * 2;
-    const int nslots = nlists * per_list;
+    const int nslots = (ni + uni(q.num_vimages)) * side * 2;
     unsigned pos = 0u, nan = 0u;
+    auto meet = [&](int j) {
+      const PHot& h = F.hot[j];
+      if (is_neighbor_h(q, h, unit, thr, nradius, true)) eb_bin(h.coord, q.coord, xdir, ydir, radiuslow, radiushigh, pos, nan);
+    };
     for (int base = 0; base < nslots; base += 64 * NB_SK) {
-      int bk[NB_SK], ck[NB_SK], hk[NB_SK];
+      NbSlot sl[NB_SK];
 #pragma unroll
       for (int k = 0; k < NB_SK; ++k) {
-        const int slot = base + k * 64 + lane;
-        int b = 0, e = 0, lst = 0, head = -1;
-        if (slot < nslots) {
-          const int li = slot / per_list;
-          int r = slot - li * per_list;
-          const int dyi = r / (2 * side);
-          r -= dyi * 2 * side;
-          const int dxi = r >> 1;
-          lst = r & 1;
-          const bool vis = li >= ni;
-          const int t = vis ? q.vimages[li - ni] : q.images[li];
-          if (t < s.tnum) {
-            const int gw = gwidth(s, t), gh = gheight(s, t);
-            const int yt = (vis ? q.vgrids[li - ni][1] : q.grids[li][1]) + dyi - margin;
-            const int xt = (vis ? q.vgrids[li - ni][0] : q.grids[li][0]) + dxi - margin;
-            if (0 <= yt && yt < gh && 0 <= xt && xt < gw) {
-              const long long c = F.tgoff[t] + (long long)yt * gw + xt;
-              const int* off = lst ? F.vp_off : F.pg_off;
-              const int lim = lst ? F.nvp : F.npg;
-              b = off[c];
-              e = off[c + 1];
-              if (b < 0 || e > lim || b > e) {
-                atomicAdd(&F.err[0], 1);
-                atomicExch(&F.err[1], 12 + lst);
-                b = 0;
-                e = 0;
-              }
-              if (F.pg_dhead) head = (lst ? F.vp_dhead : F.pg_dhead)[c];
-            }
+        sl[k] = nb_slot_decode(s, F, q, ni, base + k * 64 + lane, nslots, margin);
+        // the slot's chains at once (the order of meeting does not matter here): no barrier, so every
+        // lane walks its own row's chains, cell after cell, and only the list bounds stay live
+#pragma nounroll
+        for (int dx = 0; dx < side; ++dx) {
+          int cur[1], jm[1];
+          nb_chain_heads(F, sl[k], dx, side, cur);
+          while (cur[0] >= 0) {
+            nb_chain_step(F, cur, jm);
+            if (nb_item_ok(F, true, jm[0], 15)) meet(jm[0]);
           }
         }
-        bk[k] = b | (lst << 31);
-        ck[k] = e - b;
-        hk[k] = head;
       }
-      int mine = 0;
-#pragma unroll
-      for (int k = 0; k < NB_SK; ++k) mine += ck[k];
-      const int offl = wave_excl_scan_w(mine);
-      const int tot = uni(__shfl(offl + mine, 63));
-      {
-        int o = offl;
-#pragma unroll
-        for (int k = 0; k < NB_SK; ++k) {
-          L.sb[lane * NB_SK + k] = bk[k];
-          L.so[lane * NB_SK + k] = o;
-          o += ck[k];
-        }
-      }
-      __syncthreads();
+      const int tot = nb_round_publish(L, sl);
       for (int ib = 0; ib < tot; ib += 64 * NB_NE) {
         int jv[NB_NE];
+        nb_fetch_items(F, L, ib, tot, jv);
 #pragma unroll
-        for (int u = 0; u < NB_NE; ++u) {
-          const int idx = ib + u * 64 + lane;
-          jv[u] = -1;
-          if (idx < tot) {
-            int sidx = 0;  // the last slot whose offset is <= idx (it holds idx)
-            for (int step = 64 * NB_SK / 2; step >= 1; step >>= 1)
-              if (sidx + step < 64 * NB_SK && L.so[sidx + step] <= idx) sidx += step;
-            const int sb = L.sb[sidx];
-            const int fi = (sb & 0x7fffffff) + idx - L.so[sidx];
-            jv[u] = ((sb < 0) ? F.vp_items : F.pg_items)[fi];
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < NB_NE; ++u) {
-          const int j = jv[u];
-          if (ib + u * 64 + lane >= tot) continue;
-          if (j < 0 || j >= F.n) { atomicAdd(&F.err[0], 1); atomicExch(&F.err[1], 14); continue; }
-          const PHot& h = F.hot[j];
-          if (is_neighbor_h(q, h, unit, thr, nradius, true)) eb_bin(h.coord, q.coord, xdir, ydir, radiuslow, radiushigh, pos, nan);
-        }
+        for (int u = 0; u < NB_NE; ++u)
+          if (nb_item_ok(F, ib + u * 64 + lane < tot, jv[u], 14)) meet(jv[u]);
       }
-      // entries committed by earlier expansion waves (short chains, walked per lane)
-#pragma unroll
-      for (int k = 0; k < NB_SK; ++k)
-        for (int ent = hk[k]; ent >= 0;) {
-          const int2 en = F.d_ent[ent];
-          ent = en.y;
-          const int j = en.x;
-          if (j < 0 || j >= F.n) { atomicAdd(&F.err[0], 1); atomicExch(&F.err[1], 15); continue; }
-          const PHot& h = F.hot[j];
-          if (is_neighbor_h(q, h, unit, thr, nradius, true)) eb_bin(h.coord, q.coord, xdir, ydir, radiuslow, radiushigh, pos, nan);
-        }
       __syncthreads();
     }
-    for (int d = 32; d >= 1; d >>= 1) {
-      pos |= __shfl_xor(pos, d);
-      nan |= __shfl_xor(nan, d);
-    }
-    if (lane == 0) {
-      for (int b = 0; b < 6; ++b) {
-        int ok = 1;
-        if ((pos >> b & 1u) && !(nan >> b & 1u)) ok = 0;  // 0.0f < fill[b]
-        if (q.dflag & (0x0001 << b)) ok = 0;
-        cand_ok[6 * pk + b] = ok;
-        if (ok) {
-          // expand.cpp:176-177: the angle is stored as float, then cos/sin run in double.
-          const float angle = (float)(2 * M_PI * b / 6);
-          const double cr = cos((double)angle) * (double)radius, sr = sin((double)angle) * (double)radius;
-          for (int c = 0; c < 4; ++c)
-            cand_coord[4 * (6 * pk + b) + c] = (q.coord[c] + (float)((double)xdir[c] * cr)) + (float)((double)ydir[c] * sr);
-        }
-      }
-    }
+    eb_write_candidates(pos, nan, q, radius, xdir, ydir, pk, cand_coord, cand_ok);
     __syncthreads();
   }
 }
@@ -2497,9 +2395,7 @@ __global__ __launch_bounds__(64) NB_WALK_ATTR void depth_post_kernel(DScene s, F
   double* M = scratch + (size_t)blockIdx.x * (CAP * 8);
   double* r = M + (size_t)CAP * 5;
   for (;;) {
-    int i = 0;
-    if (lane == 0) i = atomicAdd(queue, 1);
-    i = __builtin_amdgcn_readfirstlane(i);
+    const int i = next_ticket(queue);
     if (i >= (ov.only ? *ov.only_n : m)) break;
     const int k = ov.only ? __builtin_amdgcn_readfirstlane(ov.only[i]) : i;
     const pmvs_refined& rr = res[k];
@@ -2805,8 +2701,10 @@ hipError_t FilterBuffers::ensure_entries(size_t e, int vis) {
 }
 
 // The neighbour walks' re-walk lists (NbOverflow): the NB_CAP walk appends its overflowed items to
-// B.ovf_items (count at B.counters[10]); the NB_CAP_BIG form, launched right after it without a host
-// sync (its workgroups leave at once when the list is empty), walks them (queue B.counters[11]).
+// B.ovf_items (count at B.counters[10]); the re-walk -- the NB_CAP_BIG form of neighbor_kernel and
+// depth_post_kernel, empty_blocks_stream_kernel for findEmptyBlocks -- is launched right after it
+// without a host sync (its workgroups leave at once when the list is empty) and walks them (queue
+// B.counters[11]).
 static hipError_t nb_overflow_lists(FilterBuffers& B, size_t items, hipStream_t st, NbOverflow& walk, NbOverflow& rewalk) {
   FCHK(B.ovf_items.grow_headroom(std::max<size_t>(items, 1)));
   if (!B.scratch_big) FCHK(B.scratch_big.alloc((size_t)NB_GRID_BIG * NB_CAP_BIG * 8));
@@ -3306,13 +3204,14 @@ static hipError_t filter_pass_impl(const DScene& s, FilterBuffers& B, pmvs_patch
   if (inject && inj_where == 'f') return hipErrorOutOfMemory;
   FCHK(hipMemsetAsync(B.flags, 0, n * sizeof(int), st));
   FCHK(hipMemsetAsync(B.counters + 3, 0, 5 * sizeof(int), st));
+  NbOverflow nbr;  // the re-walk's list (nb_overflow_lists), for neighbor_kernel<NB_CAP_BIG> below
   if (c.nalive) {
     // PMVS_QUAD_ROWS caps the deferred-fit rows (tests: 0 = every fit in the wave, small = a mix)
     QuadJobs qj{B.qf, B.qrows, B.qjobs, B.qctr, reinterpret_cast<int*>(B.qctr + 1), (unsigned long long)B.cap_qrows};
     if (const char* e = getenv("PMVS_QUAD_ROWS")) qj.cap_rows = std::min(qj.cap_rows, (unsigned long long)atoll(e));
     if (qj.cap_rows == 0) qj.f = nullptr;
     FCHK(hipMemsetAsync(B.qctr, 0, 2 * sizeof(unsigned long long), st));
-    NbOverflow nbw, nbr;
+    NbOverflow nbw;
     FCHK(nb_overflow_lists(B, (size_t)c.nalive, st, nbw, nbr));
     int* nbdbg = getenv("PMVS_FILTER_DEBUG") ? B.need : nullptr;
     hipLaunchKernelGGL(neighbor_kernel<NB_CAP>, dim3(std::min(grid * NB_GRID_MULT, c.nalive)), dim3(64), 0, st, s, c.dev(),
@@ -3356,9 +3255,6 @@ static hipError_t filter_pass_impl(const DScene& s, FilterBuffers& B, pmvs_patch
   }
   if (c.nalive) {  // the patches with more than NB_CAP neighbours, walked again (fits in the wavefront)
     QuadJobs qnone{};
-    NbOverflow nbr;
-    nbr.only = B.ovf_items;
-    nbr.only_n = B.counters + 10;
     hipLaunchKernelGGL(neighbor_kernel<NB_CAP_BIG>, dim3(NB_GRID_BIG), dim3(64), 0, st, s, c.dev(), B.scratch_big, B.flags,
                        B.counters + 3, B.counters + 11, getenv("PMVS_FILTER_DEBUG") ? B.need : nullptr, R, G, qnone, nbr);
   }
@@ -4361,15 +4257,14 @@ static hipError_t expand_pass_impl(const DScene& s, FilterBuffers& B, ExpandBuff
         FCHK(nb_overflow_lists(B, (size_t)(phi - plo), st, nbw, nbr));
         hipLaunchKernelGGL(empty_blocks_kernel<NB_CAP>, dim3(std::min(grid * NB_GRID_MULT, phi - plo)), dim3(64), 0, st, s,
                            c.dev(), X.parents + off + plo, phi - plo, X.cand_coord + (size_t)(off + plo) * 24,
-                           X.cand_ok + (size_t)(off + plo) * 6, B.counters + 4, B.counters + 3, nbw);
+                           X.cand_ok + (size_t)(off + plo) * 6, B.counters + 4, nbw);
         hipLaunchKernelGGL(empty_blocks_stream_kernel, dim3(NB_GRID_BIG), dim3(64), 0, st, s, c.dev(), X.parents + off + plo,
                            X.cand_coord + (size_t)(off + plo) * 24, X.cand_ok + (size_t)(off + plo) * 6, B.counters + 11,
                            nbr);
       }
       if (G > 1) {
+        // (no overflow to report: the stream re-walk has no capacity)
         hipError_t lerr = hipPeekAtLastError();
-        int ovf = 0;
-        if (lerr == hipSuccess) lerr = read_int(B.counters + 3, &ovf, st);
         if (inject && inj_where == 'e' && stats[7] == inj_wave) lerr = hipErrorOutOfMemory;
         const size_t pb = (size_t)pch * (24 * sizeof(float) + 6 * sizeof(int));
         const bool dev = (bool)sh.exchange_dev;
@@ -4392,16 +4287,13 @@ static hipError_t expand_pass_impl(const DScene& s, FilterBuffers& B, ExpandBuff
           if (lerr == hipSuccess) lerr = pack(xsend.data(), hipMemcpyDeviceToHost);
           if (lerr == hipSuccess) lerr = hipStreamSynchronize(st);
         }
-        int hdr[2] = {(int)lerr, ovf};
+        int hdr[2] = {(int)lerr, 0};
         std::vector<int> hall(2 * (size_t)G, 0);
         agreed = true;  // the header below is this chunk's terminal exchange for a failing rank
         if (sh.exchange(hdr, sizeof(hdr), hall.data()) != 0) return hipErrorUnknown;
-        for (int r = 0; r < G; ++r) {
+        for (int r = 0; r < G; ++r)
           if (hall[2 * r] != 0 && lerr == hipSuccess) lerr = hipErrorUnknown;  // another rank failed
-          ovf |= hall[2 * r + 1];
-        }
         FCHK(lerr);
-        if (ovf) { trace_error(kCapacityOverflow, __LINE__); return kCapacityOverflow; }  // more than NB_CAP neighbours (reported by the API)
         if (dev ? sh.exchange_dev(X.xsd, pb, X.xrd, st) != 0 : sh.exchange(xsend.data(), pb, xrecv.data()) != 0)
           return hipErrorUnknown;
         agreed = false;

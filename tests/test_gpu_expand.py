@@ -245,9 +245,11 @@ def test_sharded_full_loop_matches_single_rank(gpu_available):
 def test_expand_min_candidates_matches_oracle(gpu_available, oracle_mod, monkeypatch, depth, softcap):
     """Waves extended by further parent chunks until they hold min_candidates free directions
     (the schedule bench.py uses for C3): device and oracle run the same schedule.  PMVS_NB_SOFTCAP=8:
-    findEmptyBlocks' and check()'s neighbour walks go through the NB_CAP_BIG re-walk."""
+    every walk with more than 8 neighbours overflows, so findEmptyBlocks' parents are walked again by
+    the bufferless stream form (empty_blocks_stream_kernel, over CSR lists and delta chains) and
+    check()'s candidates, at depth 2, by the NB_CAP_BIG form of depth_post_kernel."""
     import pmvs_amd as P
-    if softcap is not None:  # findEmptyBlocks / depth >= 2 check() walks re-walked by the NB_CAP_BIG form
+    if softcap is not None:  # findEmptyBlocks re-walked by the stream form, depth >= 2 check() by the NB_CAP_BIG form
         monkeypatch.setenv("PMVS_NB_SOFTCAP", softcap)
     inp, p = P.synth_scene(6, 480, 360, level=1, supersample=2)
     g = P.Scene(inp)

@@ -98,7 +98,8 @@ def test_filter_quad_deferral_paths(gpu_available, oracle_mod, monkeypatch, cap,
     full; PMVS_QUAD_ROWS caps that buffer so both paths (and a mix) meet the oracle.
     PMVS_QUAD_WAVES_PER_CU = 1 caps the lane kernel's grid, so each lane fits several jobs
     (the grid-stride path); PMVS_QUAD_LDS_ROWS = 12 splits the fits between the two kernels.
-    PMVS_NB_SOFTCAP = 8: the neighbour walk's overflow path (the NB_CAP_BIG re-walk)."""
+    PMVS_NB_SOFTCAP = 8: the neighbour walk's overflow path (filterNeighbor's patches are walked
+    again by neighbor_kernel's NB_CAP_BIG form; only findEmptyBlocks has the stream re-walk)."""
     import pmvs_amd as P
     if cap != "-1":
         monkeypatch.setenv("PMVS_QUAD_ROWS", cap)
