@@ -1760,6 +1760,20 @@ pmvs_status pmvs_selftest_format(int32_t device, int32_t precision, const float*
   return PMVS_OK;
 }
 
+pmvs_status pmvs_selftest_labels(int32_t device, int32_t n, const int32_t* edge_off, const int32_t* edges, int32_t* lab_out,
+                                 int32_t* stats_out) {
+  if (n <= 0 || !edge_off || !lab_out || !stats_out || edge_off[0] != 0) return fail(PMVS_EINVAL, "invalid argument");
+  for (int i = 0; i < n; ++i)
+    if (edge_off[i + 1] < edge_off[i]) return fail(PMVS_EINVAL, "edge_off decreases at %d", i);
+  if (edge_off[n] > 0 && !edges) return fail(PMVS_EINVAL, "invalid argument");
+  for (int e = 0; e < edge_off[n]; ++e)
+    if (edges[e] < 0 || edges[e] >= n) return fail(PMVS_EINVAL, "edge %d leaves the graph", e);
+  HIPCHK(hipSetDevice(device));
+  const hipError_t e = labels_selftest(edge_off, edges, n, lab_out, stats_out);
+  if (e != hipSuccess) return fail(PMVS_EDEVICE, "labels selftest: %s", hipGetErrorString(e));
+  return PMVS_OK;
+}
+
 pmvs_status pmvs_scene_set_shard(pmvs_scene* sc, int32_t rank, int32_t world, pmvs_allgather_fn fn, void* ctx) {
   if (!sc || world < 1 || rank < 0 || rank >= world || (world > 1 && !fn)) return fail(PMVS_EINVAL, "invalid shard");
   sc->shard_rank = rank;

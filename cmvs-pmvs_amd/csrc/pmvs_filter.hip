@@ -2929,47 +2929,163 @@ __global__ void unpack_bits_kernel(const unsigned* __restrict__ bits, int n, int
   if (k < n) f[k] = (bits[k >> 5] >> (k & 31)) & 1u;
 }
 
-// filterSmallGroups labels on the device (filter_pass): see the comment at the call.
-static int lab_jump() {  // PMVS_LAB_JUMP: sweeps per all-vertex pointer jump (A/B knob)
-  static const int v = getenv("PMVS_LAB_JUMP") ? std::max(1, atoi(getenv("PMVS_LAB_JUMP"))) : 1;
-  return v;
-}
-__global__ void lab_init_kernel(int* __restrict__ lab, int* __restrict__ active, int na) {
+// filterSmallGroups labels on the device (label_stage below; the reference's BFS at filter.cpp:520-562).
+// The label of vertex j is the smallest collect index from which j is reachable over the directed
+// neighbour edges.  Two vertices joined by a mutual edge pair (i -> j and j -> i) reach each other, so
+// they have the same ancestors and the same label: every set connected by mutual pairs is contracted
+// into one supernode (union-find), and the fixpoint slab[r] = min(r, slab of the sets with an edge into
+// r) runs on the contracted graph over the few edges whose ends lie in different sets.  The label is
+// the minimum member of some set (if m reaches j, so does the minimum of m's set), which is the set's
+// root here.  Weak components (union over every edge) would not do: i -> j without j -> i gives j the
+// label of i but not i the label of j.
+//
+// Visibility across workgroups.  The per-XCD L2s are not coherent and a CU's L1 is not refreshed by
+// other CUs' stores, so a plain load inside a kernel may return an old value.  Nothing here needs a
+// fresh one:
+//  * parent[x] only ever holds ancestors of x in x's set, each smaller than the one before (x itself at
+//    first; the larger root is hooked under the smaller, and lab_find's shortcuts store a grandparent
+//    with atomicMin), so a walk over old values still climbs x's own tree and ends: it can stop at a
+//    vertex that has stopped being a root, and the hook, a device-scope atomicCAS(parent[r], r, .),
+//    then fails and returns the current parent, from which the walk goes on.  Only a CAS hooks a root
+//    and a vertex seen as hooked stays hooked, so the final root of a set is its minimum member
+//    whatever the interleaving, and the labels are the same in every run and on every rank.
+//  * slab[r] only decreases, by atomicMin, to the root of a set that reaches r.  A sweep that reads an
+//    old (larger) value tries an atomicMin that does nothing, or misses a value that another thread
+//    lowered during the same sweep -- which set `changed`, so another sweep follows.  A batch of
+//    sweeps that changed nothing wrote nothing, so all its reads were current: the fixpoint.
+// Phases that read what an earlier phase wrote are separate launches.
+__global__ void lab_init_kernel(int* __restrict__ parent, int na) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < na) {
-    lab[i] = i;
-    active[i] = 1;
-  }
+  if (i < na) parent[i] = i;
 }
-// One relaxation sweep over the vertices whose label dropped since they were last relaxed
-// (active[i] != 0), or over every vertex (all = 1: the verifying sweep).  A lowered target is
-// re-activated; the sweep's reads of other vertices' labels may already see this sweep's updates
-// (labels only decrease, so any interleaving converges to the same fixpoint).
-// jump: whether every vertex tries the pointer jump in this sweep (else only the active ones do: an
-// inactive vertex then costs one coalesced flag read, not the jump's dependent gather).
-__global__ void lab_relax_kernel(const int* __restrict__ eoff, const int* __restrict__ edges, int na, int* lab,
-                                 int* active, int all, int* changed, int jump) {
+// The root reached from x, every vertex on the way re-pointed at its grandparent.
+__device__ __forceinline__ int lab_find(int* parent, int x) {
+  int p = parent[x];
+  while (p != x) {
+    const int g = parent[p];
+    if (g != p) atomicMin(&parent[x], g);
+    x = p;
+    p = g;
+  }
+  return x;
+}
+// Mutual test and hook, one thread per vertex: the pair {i, j}, i < j, is handled by i's thread when
+// i -> j is an edge and i is found in j's list (skipped when the two are already in one set).
+__global__ void lab_hook_kernel(const int* __restrict__ eoff, const int* __restrict__ edges, int na, int* parent) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= na) return;
-  if (!all && !jump && active[i] == 0) return;
-  // the pointer jump lab[i] = lab[lab[i]] (reachability is transitive), fused here (round 4 ran it as
-  // its own full pass after every other sweep); a jumped vertex relaxes too
-  const int l0 = lab[i], l1 = lab[l0];
-  const bool jumped = l1 < l0 && atomicMin(&lab[i], l1) > l1;
-  if (jumped) atomicOr(changed, 1);
-  // a plain read first (a flag set during this sweep and read stale stays set for the next)
-  if (!all && !jumped && active[i] == 0) return;
-  if (atomicExch(&active[i], 0) == 0 && !all && !jumped) return;
-  const int li = atomicAdd(&lab[i], 0);
-  bool any = false;
+  int ri = i;
   for (int e = eoff[i]; e < eoff[i + 1]; ++e) {
     const int j = edges[e];
-    if (li < lab[j] && atomicMin(&lab[j], li) > li) {
-      atomicOr(&active[j], 1);
-      any = true;
+    if (j <= i) continue;
+    ri = lab_find(parent, ri);
+    int rj = lab_find(parent, j);
+    if (ri == rj) continue;
+    bool mutual = false;
+    for (int f = eoff[j]; f < eoff[j + 1] && !mutual; ++f) mutual = edges[f] == i;
+    if (!mutual) continue;
+    while (ri != rj) {
+      const int hi = max(ri, rj), lo = min(ri, rj);
+      const int old = atomicCAS(&parent[hi], hi, lo);
+      if (old == hi) {
+        ri = rj = lo;
+        break;
+      }
+      ri = lab_find(parent, old);  // hi was hooked meanwhile: go on from its parent
+      rj = lab_find(parent, lo);
     }
   }
+}
+// root[i] = the root of i's set; parent[] is only read, so it stays slab[] for the roots (slab[r] = r).
+__global__ void lab_flatten_kernel(const int* __restrict__ parent, int na, int* __restrict__ root, int* __restrict__ nsuper) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  int x = i;
+  if (i < na) {
+    for (int p = parent[x]; p != x; p = parent[x]) x = p;
+    root[i] = x;
+  }
+  const unsigned long long roots = __ballot(i < na && x == i);
+  if ((threadIdx.x & 63) == 0 && roots) atomicAdd(nsuper, (int)__popcll(roots));
+}
+// The residual vertices: those with an edge into another set.
+__global__ void lab_cross_kernel(const int* __restrict__ eoff, const int* __restrict__ edges, const int* __restrict__ root,
+                                 int na, int* __restrict__ cross) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= na) return;
+  const int ri = root[i];
+  int f = 0;
+  for (int e = eoff[i]; e < eoff[i + 1] && !f; ++e) f = root[edges[e]] != ri;
+  cross[i] = f;
+}
+__global__ void lab_residual_kernel(const int* __restrict__ cross, const int* __restrict__ off, int na, int* __restrict__ rlist) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < na && cross[i]) rlist[off[i]] = i;
+}
+// One sweep of the contracted fixpoint over the residual list: the pointer jump
+// slab[r] = min(slab[r], slab[slab[r]]) of the vertex's own set (reachability is transitive), then
+// its label into the sets its cross edges enter.
+__global__ void lab_sweep_kernel(const int* __restrict__ eoff, const int* __restrict__ edges, const int* __restrict__ root,
+                                 const int* __restrict__ rlist, int nres, int* slab, int* changed) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nres) return;
+  const int i = rlist[t], ri = root[i];
+  int li = slab[ri];
+  bool any = false;
+  const int g = slab[li];
+  if (g < li) {
+    any = atomicMin(&slab[ri], g) > g;
+    li = g;
+  }
+  for (int e = eoff[i]; e < eoff[i + 1]; ++e) {
+    const int rj = root[edges[e]];
+    if (rj != ri && li < slab[rj] && atomicMin(&slab[rj], li) > li) any = true;
+  }
   if (any) atomicOr(changed, 1);
+}
+// lab[i] = slab[root[i]], in place in root[]
+__global__ void lab_assign_kernel(const int* __restrict__ slab, int na, int* __restrict__ root) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < na) root[i] = slab[root[i]];
+}
+// The label stage on the CSR graph (eoff, edges) of na vertices.  parent, lab and rlist hold na ints,
+// cross and off na + 1; ctr two ints; on return lab[] holds the labels.  stats (host, or null):
+// supernodes, residual vertices, sweeps.  Two host reads for a graph that contracts well: the residual
+// count and the first batch's `changed`.
+struct LabelWork {
+  int *parent, *lab, *cross, *off, *rlist, *ctr;
+};
+static hipError_t label_stage(const int* eoff, const int* edges, int na, const LabelWork& W, DevBuf<char>& temp,
+                              hipStream_t st, int* stats) {
+  const dim3 grid(nblk(na)), blk(256);
+  int* const changed = W.ctr;
+  int* const nsuper = W.ctr + 1;
+  FCHK(hipMemsetAsync(W.ctr, 0, 2 * sizeof(int), st));
+  hipLaunchKernelGGL(lab_init_kernel, grid, blk, 0, st, W.parent, na);
+  hipLaunchKernelGGL(lab_hook_kernel, grid, blk, 0, st, eoff, edges, na, W.parent);
+  hipLaunchKernelGGL(lab_flatten_kernel, grid, blk, 0, st, W.parent, na, W.lab, nsuper);
+  hipLaunchKernelGGL(lab_cross_kernel, grid, blk, 0, st, eoff, edges, W.lab, na, W.cross);
+  FCHK(hipMemsetAsync(W.cross + na, 0, sizeof(int), st));
+  FCHK(cub_run(temp, [&](void* t, size_t& tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, W.cross, W.off, na + 1, st); }));
+  int nres = 0, ns = 0, sweeps = 0;
+  FCHK(d2h_sync(st, {{&nres, W.off + na, sizeof(int)}, {&ns, nsuper, sizeof(int)}}));
+  if (nres) {
+    hipLaunchKernelGGL(lab_residual_kernel, grid, blk, 0, st, W.cross, W.off, na, W.rlist);
+    int* const slab = W.parent;
+    // batches of 2, 4, 8, 16, 16, ... sweeps, one read of `changed` each
+    for (int batch = 2;; batch = std::min(2 * batch, 16)) {
+      for (int r = 0; r < batch; ++r)
+        hipLaunchKernelGGL(lab_sweep_kernel, dim3(nblk(nres)), blk, 0, st, eoff, edges, W.lab, W.rlist, nres, slab, changed);
+      sweeps += batch;
+      int ch = 0;
+      FCHK(read_int(changed, &ch, st));
+      if (!ch) break;
+      if (sweeps > 2 * na + 32) return hipErrorIllegalState;  // cannot happen: every batch lowers some label
+      FCHK(hipMemsetAsync(changed, 0, sizeof(int), st));
+    }
+    hipLaunchKernelGGL(lab_assign_kernel, grid, blk, 0, st, slab, na, W.lab);
+  }
+  if (stats) stats[0] = ns, stats[1] = nres, stats[2] = sweeps;
+  return hipGetLastError();
 }
 // Most patches share a few labels (one big component per surface): the lanes holding the wave's
 // first label add it with one atomic, the others one each (no same-address atomic storm).
@@ -3304,33 +3420,16 @@ static hipError_t filter_pass_impl(const DScene& s, FilterBuffers& B, pmvs_patch
     // smallest collect index m from which j is reachable (m is unlabelled when its turn comes --
     // an earlier root reaching m would reach j -- and no node of a path m -> j can carry an
     // earlier label, for the same reason), so the labels are a fixpoint: lab[j] = min over edges
-    // i -> j of lab[i], accelerated by lab[j] = lab[lab[j]] (reachability is transitive).  Computed
-    // on the device; only the component sizes matter (threshold below).
+    // i -> j of lab[i].  Computed on the device, the mutual edge pairs contracted first (label_stage);
+    // only the component sizes matter (threshold below).
     const int threshold = std::max(20, na / 10000);
     int* lab = B.need;   // free after filterExact
     int* csize = B.list;
-    int* changed = B.counters + 5;
-    // Relaxation sweeps visit only the vertices whose label dropped since their last sweep (the
-    // late sweeps, a few thousand vertices, cost a launch instead of a pass over every edge); the
-    // loop ends after a sweep over EVERY vertex changes nothing, i.e. at the fixpoint itself.
-    int* active = B.list;  // csize's buffer, free until the counting below
-    hipLaunchKernelGGL(lab_init_kernel, dim3(nblk(na)), dim3(256), 0, st, lab, active, na);
-    // every lab_jump()-th active sweep jumps every vertex's pointer (1: every sweep, rounds 4-5)
-    int sweep = 0;
-    for (int it = 0;; ++it) {
-      const bool verify = (it % 9) == 8;  // a full sweep after each 8 rounds of active sweeps that changed something
-      FCHK(hipMemsetAsync(changed, 0, sizeof(int), st));
-      for (int r = 0; r < (verify ? 1 : 8); ++r) {
-        if (ne)
-          hipLaunchKernelGGL(lab_relax_kernel, dim3(nblk(na)), dim3(256), 0, st, B.edge_off, B.edges, na, lab, active,
-                             verify ? 1 : 0, changed, (sweep++ % lab_jump()) == 0 ? 1 : 0);
-      }
-      int ch = 0;
-      FCHK(read_int(changed, &ch, st));
-      if (verify && !ch) break;
-      if (!verify && !ch) it = 9 * (it / 9) + 7;  // nothing moved: verify next
-      if (it > 9 * (na + 1)) return hipErrorIllegalState;  // cannot happen: every round lowers some label
-    }
+    // the residual list shares csize's buffer (free until the counting below); cnt / off are free
+    // once the edges are written
+    FCHK(B.lparent.grow_headroom((size_t)na));
+    FCHK(label_stage(B.edge_off, B.edges, na, LabelWork{B.lparent, lab, B.cnt, B.off, B.list, B.counters + 12}, B.temp, st,
+                     nullptr));
     FCHK(hipMemsetAsync(csize, 0, na * sizeof(int), st));
     hipLaunchKernelGGL(lab_count_kernel, dim3(nblk(na)), dim3(256), 0, st, lab, na, csize);
     FCHK(hipMemsetAsync(B.flags, 0, n * sizeof(int), st));
@@ -3371,6 +3470,20 @@ static void nb_prof_dump(const char* what) {
 #else
   (void)what;
 #endif
+}
+
+hipError_t labels_selftest(const int* h_eoff, const int* h_edges, int n, int* h_lab, int stats[3]) {
+  const int ne = h_eoff[n];
+  DevBuf<int> eoff, edges, parent, lab, cross, off, rlist, ctr;
+  DevBuf<char> temp;
+  FCHK(eoff.alloc((size_t)n + 1)); FCHK(edges.alloc((size_t)ne)); FCHK(parent.alloc((size_t)n)); FCHK(lab.alloc((size_t)n));
+  FCHK(cross.alloc((size_t)n + 1)); FCHK(off.alloc((size_t)n + 1)); FCHK(rlist.alloc((size_t)n)); FCHK(ctr.alloc(2));
+  FCHK(hipMemcpy(eoff, h_eoff, ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice));
+  if (ne) FCHK(hipMemcpy(edges, h_edges, (size_t)ne * sizeof(int), hipMemcpyHostToDevice));
+  const hipError_t e = label_stage(eoff, edges, n, LabelWork{parent, lab, cross, off, rlist, ctr}, temp, nullptr, stats);
+  d2h_stage_release(nullptr);
+  FCHK(e);
+  return hipMemcpy(h_lab, lab, (size_t)n * sizeof(int), hipMemcpyDeviceToHost);
 }
 
 hipError_t filter_pass(const DScene& s, FilterBuffers& B, pmvs_patch* dP, int n, long long ncells, const long long* h_tgoff,

@@ -182,6 +182,7 @@ struct FilterBuffers {
   DevBuf<unsigned long long> vrows, used;
   DevBuf<float4> normalc;
   DevBuf<int> refpos;
+  DevBuf<int> lparent;  // filterSmallGroups: the union-find parents, then the supernodes' labels (label_stage)
   DevBuf<char> xr;
   // filterNeighbor's deferred quadric fits (pmvs_filter.hip QuadJobs)
   DevBuf<float> qf;
@@ -299,6 +300,10 @@ using CompactDst = std::function<hipError_t(int, pmvs_patch**)>;
 hipError_t compact_model(FilterBuffers& B, const pmvs_patch* src, int n, const int* keep, const CompactDst& dst_for,
                          int* nkept, hipStream_t st);
 hipError_t fill_int(int* a, int n, int v, hipStream_t st);
+// filterSmallGroups' label stage, as filter_pass runs it, on a host CSR graph of n vertices (edges in
+// [0, n)): h_lab[j] = the smallest vertex from which j is reachable; stats = supernodes, residual
+// vertices, sweeps.
+hipError_t labels_selftest(const int* h_eoff, const int* h_edges, int n, int* h_lab, int stats[3]);
 // frees the device-to-host staging buffers of a scene's stream (pmvs_scene_destroy)
 void d2h_stage_release(hipStream_t st);
 

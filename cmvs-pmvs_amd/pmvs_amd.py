@@ -164,7 +164,7 @@ EXPORTS = ["pmvs_last_error", "pmvs_device_count", "pmvs_scene_create", "pmvs_sc
            "pmvs_expand_run", "pmvs_expand_fetch", "pmvs_run_loop", "pmvs_loop_fetch", "pmvs_loop_hash",
            "pmvs_loop_export_sizes", "pmvs_loop_export", "pmvs_export_patches_sizes", "pmvs_export_patches",
            "pmvs_depth_map_layout", "pmvs_loop_depth_maps", "pmvs_depth_maps_patches", "pmvs_write_pfm",
-           "pmvs_loop_text", "pmvs_text_patches", "pmvs_selftest_format",
+           "pmvs_loop_text", "pmvs_text_patches", "pmvs_selftest_format", "pmvs_selftest_labels",
            "pmvs_scene_set_shard", "pmvs_scene_set_shard_rccl", "pmvs_scene_set_cluster",
            "pmvs_scene_set_cluster_rccl", "pmvs_rccl_unique_id",
            "pmvs_rccl_create", "pmvs_rccl_destroy", "pmvs_rccl_allgather", "pmvs_rccl_allgather_device",
@@ -245,6 +245,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.pmvs_text_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                       C.c_int64, C.POINTER(C.c_int64)]
     lib.pmvs_selftest_format.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.pmvs_selftest_labels.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pmvs_scene_set_shard.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.pmvs_scene_set_cluster.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pmvs_scene_set_cluster_rccl.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
@@ -767,6 +768,20 @@ def selftest_format(precision: int, x: np.ndarray, device: int = 0):
         _check(load_library().pmvs_selftest_format(device, precision, _ptr(x), len(x), _ptr(out), _ptr(ln)))
     raw = out.tobytes()
     return [raw[24 * i:24 * i + int(k)] for i, k in enumerate(ln)]
+
+
+def selftest_labels(edge_off: np.ndarray, edges: np.ndarray, device: int = 0):
+    """pmvs_selftest_labels: filterSmallGroups' label stage on a directed CSR graph (vertex i's targets are
+    edges[edge_off[i]:edge_off[i + 1]]).  Returns (labels, stats): labels[j] = the smallest vertex from which
+    j is reachable; stats = {"supernodes", "residual", "sweeps"}."""
+    edge_off = np.ascontiguousarray(edge_off, np.int32).reshape(-1)
+    edges = np.ascontiguousarray(edges, np.int32).reshape(-1)
+    n = len(edge_off) - 1
+    lab = np.zeros(max(n, 0), np.int32)
+    stats = np.zeros(3, np.int32)
+    keep = edges if len(edges) else np.zeros(1, np.int32)
+    _check(load_library().pmvs_selftest_labels(device, n, _ptr(edge_off), _ptr(keep), _ptr(lab), _ptr(stats)))
+    return lab, {"supernodes": int(stats[0]), "residual": int(stats[1]), "sweeps": int(stats[2])}
 
 
 def selftest_lls(systems, device: int = 0) -> np.ndarray:

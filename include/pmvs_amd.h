@@ -441,6 +441,14 @@ pmvs_status pmvs_text_patches(pmvs_scene* scene, const pmvs_patch* patches, int3
  * (PMVS_EINVAL otherwise). */
 pmvs_status pmvs_selftest_format(int32_t device, int32_t precision, const float* in, int32_t n,
                                  char* out /* n x 24 */, int32_t* len /* n */);
+/* Self-test of filterSmallGroups' label stage, exactly as the filter pass runs it, on a caller's directed
+ * graph in CSR form: the edges of vertex i are i -> edges[e], e in [edge_off[i], edge_off[i + 1]), with
+ * edge_off[0] = 0 and every target in [0, n) (PMVS_EINVAL otherwise).  lab_out[j] = the smallest vertex
+ * from which j is reachable (j itself included).  stats_out: the number of sets left after contracting
+ * the mutual edge pairs, the number of vertices with an edge into another set, and the number of
+ * sweeps of the contracted fixpoint. */
+pmvs_status pmvs_selftest_labels(int32_t device, int32_t n, const int32_t* edge_off, const int32_t* edges,
+                                 int32_t* lab_out /* n */, int32_t* stats_out /* 3 */);
 
 /* The seed phase, PMVS3::CSeed::init + run (seed.cpp:11-107) at CPU 1: target images in the
  * reference's std::shuffle(mt19937(42)) order, cells in raster order, the feature points of every
