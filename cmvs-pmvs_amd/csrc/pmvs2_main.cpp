@@ -1,4 +1,4 @@
-// pmvs2_main.cpp -- the `pmvs2 prefix option_file [PATCH] [PSET] [DEPTH]` executable (reference
+// pmvs2_main.cpp -- the `pmvs2 prefix option_file [PATCH] [PSET] [DEPTH] [PIXDEPTH]` executable (reference
 // source/pmvs.cpp:7-63 with CFindMatch::init / run / write, findMatch.cpp:30-224), driving the
 // MI355X-native core through its C-ABI (include/pmvs_amd.h).  A drop-in for the program
 // genOption's pmvs.sh calls (genOption.cpp:73): same arguments, same input tree
@@ -126,11 +126,15 @@ void usage(const char* argv0) {
             << "oimages  5  0 2 4 6 8 (enumeration)" << std::endl
             << "        -1  24 48 (range specification)" << std::endl
             << std::endl
-            << "[Optional export] PATCH PSET DEPTH" << std::endl
+            << "[Optional export] PATCH PSET DEPTH PIXDEPTH" << std::endl
             << " i.e export patch and pset: prefix option_file PATCH PSET"
             << " i.e export patch only: prefix option_file PATCH" << std::endl
             << " DEPTH: every target image's depth map, one value per csize x csize cell, as" << std::endl
-            << "        models/option_file.depth.<8-digit image number>.pfm (0 = no patch)" << std::endl;
+            << "        models/option_file.depth.<8-digit image number>.pfm (0 = no patch)" << std::endl
+            << " PIXDEPTH: every target image's depth map, one value per pixel at the option's level, every" << std::endl
+            << "        patch rendered as a plane element of radius csize (at most " << PMVS_PIXEL_MAX_RADIUS
+            << ") pixels, as" << std::endl
+            << "        models/option_file.pixdepth.<8-digit image number>.pfm (0 = no patch)" << std::endl;
 }
 
 }  // namespace
@@ -143,11 +147,12 @@ int main(int argc, char* argv[]) {
   for (int i = 0; i < argc; ++i) std::cout << std::endl << argv[i];
   std::cout << std::endl;
   const std::string prefix = argv[1], option = argv[2];
-  bool export_patch = false, export_pset = false, export_depth = false;
+  bool export_patch = false, export_pset = false, export_depth = false, export_pixdepth = false;
   for (int i = 3; i < argc; ++i) {
     if (std::string(argv[i]) == "PATCH") export_patch = true;
     if (std::string(argv[i]) == "PSET") export_pset = true;
     if (std::string(argv[i]) == "DEPTH") export_depth = true;
+    if (std::string(argv[i]) == "PIXDEPTH") export_pixdepth = true;
   }
   const double t0 = now_s();
 
@@ -429,6 +434,23 @@ int main(int argc, char* argv[]) {
       char name[32];
       std::snprintf(name, sizeof(name), ".depth.%08d.pfm", images[t]);
       CHECK("pfm", pmvs_write_pfm((out + name).c_str(), dims[2 * t], dims[2 * t + 1], depth.data() + doff[t]));
+    }
+  }
+  if (export_pixdepth) {
+    // the model just written rendered into every target image (pmvs_loop_pixel_maps, writer order): one
+    // call and one PFM per target, so the host holds one image at a time
+    const int radius = std::min<int>(opt->csize, PMVS_PIXEL_MAX_RADIUS);
+    for (int t = 0; t < tnum; ++t) {
+      int32_t dims[2];
+      int64_t poff[2];
+      CHECK("pixel maps", pmvs_pixel_map_layout(sc, t, 1, dims, poff));
+      std::vector<float> depth((size_t)std::max<int64_t>(poff[1], 1));
+      pmvs_depthmap_buffers db{};
+      db.depth = depth.data();
+      CHECK("pixel maps", pmvs_loop_pixel_maps(sc, PMVS_EXPORT_WRITER_ORDER, t, 1, radius, &db));
+      char name[32];
+      std::snprintf(name, sizeof(name), ".pixdepth.%08d.pfm", images[t]);
+      CHECK("pfm", pmvs_write_pfm((out + name).c_str(), dims[0], dims[1], depth.data()));
     }
   }
   pmvs_scene_destroy(sc);

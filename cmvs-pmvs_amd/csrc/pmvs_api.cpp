@@ -1634,6 +1634,97 @@ pmvs_status pmvs_depth_maps_patches(pmvs_scene* sc, const pmvs_patch* patches, i
   return depth_maps_records(sc, dP, n, flags, buffers);
 }
 
+// ---- per-pixel maps (pmvs_pixmap.hip)
+namespace {
+bool pixel_range_ok(const pmvs_scene* sc, int32_t first, int32_t num) {
+  return first >= 0 && num > 0 && (int64_t)first + num <= sc->ds.tnum;
+}
+
+// The images of targets [first, first + num) at the scene's level and their pixel offsets; returns the total.
+int64_t pixel_map_layout(const pmvs_scene* sc, int32_t first, int32_t num, int32_t* dims, int64_t* offsets) {
+  int64_t off = 0;
+  for (int j = 0; j < num; ++j) {
+    const DView& v = sc->hviews[first + j];
+    if (dims) { dims[2 * j] = v.w[sc->ds.level]; dims[2 * j + 1] = v.h[sc->ds.level]; }
+    if (offsets) offsets[j] = off;
+    off += (int64_t)v.w[sc->ds.level] * v.h[sc->ds.level];
+  }
+  if (offsets) offsets[num] = off;
+  return off;
+}
+
+// The pixel maps of the device records dP[0, n).
+pmvs_status pixel_maps_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, int32_t flags, int32_t first, int32_t num,
+                               int32_t radius, const pmvs_depthmap_buffers* b) {
+  const bool dev = (flags & PMVS_EXPORT_DEVICE) != 0;
+  if (!b->patch && !b->depth && !b->normal && !b->ncc) return PMVS_OK;
+  const size_t pixels = (size_t)pixel_map_layout(sc, first, num, nullptr, nullptr);
+  ExportTemp tmp;
+  int* d_src = nullptr;
+  if ((flags & PMVS_EXPORT_WRITER_ORDER) && n > 0) {  // the export's order, from the export's code
+    EXPCHK(tmp.alloc(&d_src, (size_t)n));
+    EXPCHK(export_order(sc->ds, dP, n, depth_map_layout(sc, nullptr, nullptr), d_src, nullptr, nullptr, sc->stream));
+  }
+  DepthMapArrays a;
+  if (dev) {  // straight into the caller's device buffers
+    a.patch = b->patch; a.depth = b->depth; a.normal = b->normal; a.ncc = b->ncc;
+  } else {    // device staging for the requested arrays
+    if (b->patch) EXPCHK(tmp.alloc(&a.patch, pixels));
+    if (b->depth) EXPCHK(tmp.alloc(&a.depth, pixels));
+    if (b->normal) EXPCHK(tmp.alloc(&a.normal, pixels * 3));
+    if (b->ncc) EXPCHK(tmp.alloc(&a.ncc, pixels));
+  }
+  EXPCHK(pixel_map_pass(sc->ds, sc->hviews.data(), dP, n, d_src, first, num, radius, a, sc->stream));
+  if (!dev) {
+    auto down = [&](void* dst, const void* src, size_t bytes) {
+      return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sc->stream) : hipSuccess;
+    };
+    EXPCHK(down(b->patch, a.patch, pixels * sizeof(int32_t)));
+    EXPCHK(down(b->depth, a.depth, pixels * sizeof(float)));
+    EXPCHK(down(b->normal, a.normal, pixels * 3 * sizeof(float)));
+    EXPCHK(down(b->ncc, a.ncc, pixels * sizeof(float)));
+    EXPCHK(hipStreamSynchronize(sc->stream));
+  }
+  return PMVS_OK;
+}
+
+bool pixel_args_ok(const pmvs_scene* sc, int32_t flags, int32_t first, int32_t num, int32_t radius,
+                   const pmvs_depthmap_buffers* b) {
+  return sc && b && !(flags & ~(PMVS_EXPORT_WRITER_ORDER | PMVS_EXPORT_DEVICE)) && pixel_range_ok(sc, first, num) &&
+         radius >= 0 && radius <= PMVS_PIXEL_MAX_RADIUS;
+}
+}  // namespace
+
+pmvs_status pmvs_pixel_map_layout(pmvs_scene* sc, int32_t first_target, int32_t num_targets, int32_t* dims, int64_t* offsets) {
+  if (!sc || !pixel_range_ok(sc, first_target, num_targets)) return fail(PMVS_EINVAL, "invalid argument");
+  pixel_map_layout(sc, first_target, num_targets, dims, offsets);
+  return PMVS_OK;
+}
+
+pmvs_status pmvs_loop_pixel_maps(pmvs_scene* sc, int32_t flags, int32_t first_target, int32_t num_targets, int32_t radius,
+                                 const pmvs_depthmap_buffers* buffers) {
+  if (!pixel_args_ok(sc, flags, first_target, num_targets, radius, buffers)) return fail(PMVS_EINVAL, "invalid argument");
+  if (sc->lkept < 0) return fail(PMVS_EINVAL, "loop_pixel_maps: no loop result on the device");
+  HIPCHK(hipSetDevice(sc->device));
+  return pixel_maps_records(sc, sc->fpatches.p, sc->lkept, flags, first_target, num_targets, radius, buffers);
+}
+
+pmvs_status pmvs_pixel_maps_patches(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, int32_t flags, int32_t first_target,
+                                    int32_t num_targets, int32_t radius, const pmvs_depthmap_buffers* buffers) {
+  if (!pixel_args_ok(sc, flags, first_target, num_targets, radius, buffers) || n < 0 || (n > 0 && !patches))
+    return fail(PMVS_EINVAL, "invalid argument");
+  if (pmvs_status st = check_export_patches(sc, patches, n, nullptr)) return st;
+  HIPCHK(hipSetDevice(sc->device));
+  // a buffer of its own: sc->fpatches may hold a loop result
+  ExportTemp tmp;
+  pmvs_patch* dP = nullptr;
+  if (n) {
+    EXPCHK(tmp.alloc(&dP, (size_t)n));
+    EXPCHK(hipMemcpyAsync(dP, patches, (size_t)n * sizeof(pmvs_patch), hipMemcpyHostToDevice, sc->stream));
+  }
+  return pixel_maps_records(sc, dP, n, flags, first_target, num_targets, radius, buffers);
+}
+
 // ---- text files (pmvs_text.hip)
 namespace {
 bool text_args_ok(const pmvs_scene* sc, int32_t kind, int32_t flags, const char* out, int64_t cap, const int64_t* bytes) {

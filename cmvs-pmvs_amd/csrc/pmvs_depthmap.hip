@@ -78,12 +78,7 @@ __global__ __launch_bounds__(256) void depthmap_build_kernel(DScene s, const flo
   }
 }
 
-// depth_bits inverted (it maps the f32 bit patterns one to one): the winner's depth as the build kernel
-// computed it, not a second evaluation.
-__device__ __forceinline__ float depth_from_bits(unsigned int b) {
-  return __uint_as_float((b & 0x80000000u) ? (b & 0x7fffffffu) : ~b);
-}
-
+// depth_from_bits: the winner's depth as the build kernel computed it, not a second evaluation.
 __global__ __launch_bounds__(256) void depthmap_resolve_kernel(const unsigned long long* __restrict__ keys, long long cells,
                                                                const float4* __restrict__ attrc, int* __restrict__ patch,
                                                                float* __restrict__ depth, float* __restrict__ normal,
@@ -125,6 +120,14 @@ inline hipError_t blocks_for(long long items, unsigned* blocks) {
 
 }  // namespace
 
+hipError_t depth_map_pack(const pmvs_patch* P, const int* src, int n, float4* coordc, float4* attrc, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  unsigned nb = 0;
+  DCHK(blocks_for(n, &nb));
+  hipLaunchKernelGGL(depthmap_pack_kernel, dim3(nb), dim3(256), 0, st, P, src, n, coordc, attrc);
+  return hipGetLastError();
+}
+
 hipError_t depth_map_pass(const DScene& s, const pmvs_patch* P, int n, const int* src, const long long* d_off,
                           long long cells, const DepthMapArrays& out, hipStream_t st) {
   if (cells <= 0 || !(out.patch || out.depth || out.normal || out.ncc)) return hipSuccess;
@@ -136,10 +139,7 @@ hipError_t depth_map_pass(const DScene& s, const pmvs_patch* P, int n, const int
   if (n > 0) {
     DCHK(coordc.alloc((size_t)n * sizeof(float4)));
     if (attr) DCHK(attrc.alloc((size_t)n * sizeof(float4)));
-    DCHK(blocks_for(n, &nb));
-    hipLaunchKernelGGL(depthmap_pack_kernel, dim3(nb), dim3(256), 0, st, P, src, n, coordc.as<float4>(),
-                       attr ? attrc.as<float4>() : nullptr);
-    DCHK(hipGetLastError());
+    DCHK(depth_map_pack(P, src, n, coordc.as<float4>(), attr ? attrc.as<float4>() : nullptr, st));
     const int ngrp = (s.tnum + kTargetsPerThread - 1) / kTargetsPerThread;
     DCHK(blocks_for((long long)n * ngrp, &nb));
     hipLaunchKernelGGL(depthmap_build_kernel, dim3(nb), dim3(256), 0, st, s, coordc.as<float4>(), n, d_off,

@@ -90,6 +90,10 @@ __device__ __forceinline__ unsigned int depth_bits(float d) {
   const unsigned int u = __float_as_uint(d);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+// depth_bits inverted (it maps the f32 bit patterns one to one).
+__device__ __forceinline__ float depth_from_bits(unsigned int b) {
+  return __uint_as_float((b & 0x80000000u) ? (b & 0x7fffffffu) : ~b);
+}
 __device__ __forceinline__ float depth_of(const DView& v, const float* c) { return dot4(v.oaxis, c); }
 __device__ __forceinline__ int gwidth(const DScene& s, int t) { return (s.views[t].w[s.level] + s.csize - 1) / s.csize; }
 __device__ __forceinline__ int gheight(const DScene& s, int t) { return (s.views[t].h[s.level] + s.csize - 1) / s.csize; }

@@ -152,6 +152,18 @@ struct DepthMapArrays {
 // after the stream has finished the work; hipErrorOutOfMemory when its scratch cannot be allocated.
 hipError_t depth_map_pass(const DScene& s, const pmvs_patch* P, int n, const int* src, const long long* d_off,
                           long long cells, const DepthMapArrays& out, hipStream_t st);
+// The rows' float4 arrays both map passes read instead of the 1608-byte records (queued on the stream):
+// coordc[r] = the coordinate of row r (record src[r], or r when src is null) and, when attrc is not
+// null, attrc[r] = (normal x, y, z, ncc).
+hipError_t depth_map_pack(const pmvs_patch* P, const int* src, int n, float4* coordc, float4* attrc, hipStream_t st);
+
+// ---- per-pixel maps (pmvs_pixmap.hip; the definition is csrc/pmvs_pixmap.h)
+// The maps of targets [first, first + count) at `radius` over the records P[0, n) in model order (src
+// null) or with row r = record src[r], into the arrays of `out` (device pointers, pixel offsets
+// relative to target `first`).  Returns after the stream has finished the work; its scratch (32 bytes
+// per row, 8 per pixel of one group of at most eight targets) is freed by then.
+hipError_t pixel_map_pass(const DScene& s, const DView* hviews, const pmvs_patch* P, int n, const int* src, int first,
+                          int count, int radius, const DepthMapArrays& out, hipStream_t st);
 
 // ---- filter pass (pmvs_filter.hip)
 // The fields of a patch that neighbour and visibility tests read from OTHER patches (isNeighbor,

@@ -113,6 +113,7 @@ class ExportBuffers(C.Structure):  # pmvs_export_buffers
 
 
 EXPORT_WRITER_ORDER, EXPORT_DEVICE = 1, 2
+PIXEL_MAX_RADIUS = 16  # PMVS_PIXEL_MAX_RADIUS
 TEXT_PLY, TEXT_PATCH, TEXT_PSET = 0, 1, 2  # PMVS_TEXT_*: the kinds of pmvs_loop_text / pmvs_text_patches
 
 
@@ -164,6 +165,7 @@ EXPORTS = ["pmvs_last_error", "pmvs_device_count", "pmvs_scene_create", "pmvs_sc
            "pmvs_expand_run", "pmvs_expand_fetch", "pmvs_run_loop", "pmvs_loop_fetch", "pmvs_loop_hash",
            "pmvs_loop_export_sizes", "pmvs_loop_export", "pmvs_export_patches_sizes", "pmvs_export_patches",
            "pmvs_depth_map_layout", "pmvs_loop_depth_maps", "pmvs_depth_maps_patches", "pmvs_write_pfm",
+           "pmvs_pixel_map_layout", "pmvs_loop_pixel_maps", "pmvs_pixel_maps_patches",
            "pmvs_loop_text", "pmvs_text_patches", "pmvs_selftest_format", "pmvs_selftest_labels",
            "pmvs_scene_set_shard", "pmvs_scene_set_shard_rccl", "pmvs_scene_set_cluster",
            "pmvs_scene_set_cluster_rccl", "pmvs_rccl_unique_id",
@@ -240,6 +242,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.pmvs_loop_depth_maps.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DepthMapBuffers)]
     lib.pmvs_depth_maps_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DepthMapBuffers)]
     lib.pmvs_write_pfm.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.pmvs_pixel_map_layout.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.pmvs_loop_pixel_maps.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DepthMapBuffers)]
+    lib.pmvs_pixel_maps_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                            C.POINTER(DepthMapBuffers)]
     lib.pmvs_loop_text.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                    C.POINTER(C.c_int64)]
     lib.pmvs_text_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -640,10 +646,11 @@ class Scene:
         _check(self.lib.pmvs_depth_map_layout(self.handle, _ptr(dims), _ptr(off)))
         return dims, off
 
-    def _depth_map_buffers(self, device: bool, arrays):
-        """The arrays of one depth-map call and the pmvs_depthmap_buffers that points at them, by
-        _export_buffers' conventions."""
-        cells = int(self.depth_map_layout()[1][-1])
+    def _depth_map_buffers(self, device: bool, arrays, cells=None):
+        """The arrays of one depth-map call (or, with `cells` pixels, of one pixel-map call) and the
+        pmvs_depthmap_buffers that points at them, by _export_buffers' conventions."""
+        if cells is None:
+            cells = int(self.depth_map_layout()[1][-1])
         names = list(self.DEPTH_MAP_ARRAYS) if arrays is None else list(arrays)
         out, buf = {}, DepthMapBuffers()
         for k in names:
@@ -678,6 +685,43 @@ class Scene:
         flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
         _check(self.lib.pmvs_depth_maps_patches(self.handle, _ptr(pa), len(pa), flags, C.byref(buf)))
         return out
+
+    def pixel_map_layout(self, first_target: int = 0, num_targets=None):
+        """pmvs_pixel_map_layout: (dims [n, 2] int32 = the (width, height) of targets [first_target,
+        first_target + num_targets) at the scene's level, offsets [n + 1] int64 = the first pixel of each
+        target's map relative to the first, the last entry the total).  num_targets None: all from
+        first_target on."""
+        num = self.desc.num_targets - first_target if num_targets is None else num_targets
+        dims, off = np.zeros((max(num, 0), 2), np.int32), np.zeros(max(num, 0) + 1, np.int64)
+        _check(self.lib.pmvs_pixel_map_layout(self.handle, first_target, num, _ptr(dims), _ptr(off)))
+        return dims, off
+
+    def _pixel_map_call(self, call, writer_order, device, arrays, first_target, num_targets, radius):
+        num = self.desc.num_targets - first_target if num_targets is None else num_targets
+        radius = self.desc.csize if radius is None else radius
+        out, buf = self._depth_map_buffers(device, arrays, int(self.pixel_map_layout(first_target, num)[1][-1]))
+        flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
+        _check(call(flags, first_target, num, radius, C.byref(buf)))
+        return out
+
+    def loop_pixel_maps(self, writer_order: bool = True, device: bool = False, arrays=None, first_target: int = 0,
+                        num_targets=None, radius=None) -> dict:
+        """pmvs_loop_pixel_maps: the last run_loop(fetch=False) result rendered into targets
+        [first_target, first_target + num_targets) (None: all from first_target on), one value per pixel
+        at the scene's level, every patch a plane element of `radius` pixels (None: csize) around its
+        projection; keyed as loop_depth_maps: patch [pixels] (-1 = empty), depth [pixels], normal
+        [pixels, 3], ncc [pixels].  pixel_map_layout() of the same range gives each target's pixels and
+        depth_map_view one target's image.  Does not consume the result.  device=True: torch tensors on
+        the scene's device, written there.  arrays: the names wanted (None = all)."""
+        return self._pixel_map_call(lambda *a: self.lib.pmvs_loop_pixel_maps(self.handle, *a), writer_order, device,
+                                    arrays, first_target, num_targets, radius)
+
+    def pixel_maps_patches(self, patches: np.ndarray, writer_order: bool = True, device: bool = False, arrays=None,
+                           first_target: int = 0, num_targets=None, radius=None) -> dict:
+        """pmvs_pixel_maps_patches: loop_pixel_maps' arrays for caller-supplied PATCH_DTYPE records."""
+        pa = np.ascontiguousarray(patches, PATCH_DTYPE)
+        return self._pixel_map_call(lambda *a: self.lib.pmvs_pixel_maps_patches(self.handle, _ptr(pa), len(pa), *a),
+                                    writer_order, device, arrays, first_target, num_targets, radius)
 
     def _text(self, call, device: bool, out):
         """A size query, the buffer (numpy uint8, or a torch uint8 tensor on the scene's device; `out`

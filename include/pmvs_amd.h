@@ -411,6 +411,49 @@ pmvs_status pmvs_loop_depth_maps(pmvs_scene* scene, int32_t flags, const pmvs_de
 pmvs_status pmvs_depth_maps_patches(pmvs_scene* scene, const pmvs_patch* patches, int32_t n, int32_t flags,
                                     const pmvs_depthmap_buffers* buffers);
 
+/* The model rendered into the target images: one depth and one normal per pixel at the scene's level,
+ * every patch taken as the oriented plane element its centre and normal are.  The depth maps above hold
+ * one flat value per csize x csize cell (what visibility tests want); these maps are what depth-map
+ * fusion, meshing and texturing want.  The definition (csrc/pmvs_pixmap.h implements it once, for host
+ * and device), for target t with W x H = its image at the scene's level, and row r with f32 coord X and
+ * normal N:
+ *  1. (x, y) = CCamera::project(view t, X, level) and z = OpticalAxis(t) * X, the f32 values of the
+ *     depth maps.
+ *  2. Footprint: cx = floor((double)x + 0.5), cy likewise; the integer pixels cx-R <= u <= cx+R,
+ *     cy-R <= v <= cy+R that lie in [0, W) x [0, H), R = the call's radius.  Compared in double: project's
+ *     clamped values cannot wrap, a NaN fails.  A row with an empty footprint contributes nothing.
+ *  3. The depth d at pixel (u, v), in f64 from the f32 inputs, unfused, sums left to right:
+ *     V = centre(t) - X, nv = N.V, nn = N.N, vv = V.V (3 components).  If nv > 0 and
+ *     nv*nv >= 0.0625*(nn*vv) (the patch faces the camera within ~75.5 degrees): with P the target's 3x4
+ *     projection at the level, a = P0 - u*P2, b = P1 - v*P2 (4-vectors; a3, b3 their first three
+ *     components), solve [a3; b3; N] S = (-a_w, -b_w, N.X) by Cramer's rule: det = a3.(b3 x N),
+ *     S = ((-a_w)*(b3 x N) + (-b_w)*(N x a3) + (N.X)*(a3 x b3)) / det, and
+ *     d = (float)(oaxis0*S0 + oaxis1*S1 + oaxis2*S2 + oaxis3): OpticalAxis * (the point where the
+ *     pixel's ray meets the patch's plane).  Otherwise, or when that d is not finite or <= 0: d = z.
+ *  4. A pixel keeps the minimum key (depth_bits(d) << 32) | r: the smallest depth and, at equal depths,
+ *     the earlier row (the depth maps' rule).  The minimum does not depend on the order of arrival.
+ *  5. Per pixel, the arrays of pmvs_depthmap_buffers: patch (the row, -1 = empty), depth (the key's d),
+ *     normal x 3 and ncc of the winner; empty pixels -1 / +0.0.  Any pointer may be NULL.
+ * Layout: the maps of targets [first_target, first_target + num_targets), each row-major H rows of W
+ * pixels, target first_target + j at pixel offsets[j] of every array (64-bit: a C5 cluster passes 2^31
+ * pixels).  The range bounds memory: a buffer holds 4 (normal: 12) bytes per pixel of the range.
+ * flags, rows, record validation and the use of the loop's result are those of the depth-map calls.
+ * PMVS_EINVAL: a NULL scene or buffers, another flag bit, an empty range or one outside the scene's
+ * targets, a radius outside 0..PMVS_PIXEL_MAX_RADIUS, no loop result.  Scratch (32 bytes per row, 8 per
+ * pixel of at most eight targets at a time, and in host mode the maps) is allocated for the call and
+ * freed on return; the call returns after its work has finished. */
+#define PMVS_PIXEL_MAX_RADIUS 16
+/* dims: num_targets x 2 (width, height at the scene's level); offsets: num_targets + 1 pixels, relative to
+ * first_target (the last entry is the total).  Host arrays; either may be NULL. */
+pmvs_status pmvs_pixel_map_layout(pmvs_scene* scene, int32_t first_target, int32_t num_targets, int32_t* dims,
+                                  int64_t* offsets);
+pmvs_status pmvs_loop_pixel_maps(pmvs_scene* scene, int32_t flags, int32_t first_target, int32_t num_targets,
+                                 int32_t radius, const pmvs_depthmap_buffers* buffers);
+/* The same for caller-supplied records, as pmvs_depth_maps_patches.  n = 0 gives all-empty maps. */
+pmvs_status pmvs_pixel_maps_patches(pmvs_scene* scene, const pmvs_patch* patches, int32_t n, int32_t flags,
+                                    int32_t first_target, int32_t num_targets, int32_t radius,
+                                    const pmvs_depthmap_buffers* buffers);
+
 /* The .ply / .patch / .pset text of the model, formatted on the device: the bytes pmvs_write_ply /
  * pmvs_write_patches / pmvs_write_pset write from the export of the same records and flags
  * (CPatchOrganizerS::writePLY patchOrganizerS.cpp:687-776, writePatches2 :89-132 with Patch::operator<<
