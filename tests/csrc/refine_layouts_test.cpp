@@ -2,10 +2,15 @@
 // accepts and decodes, what it rejects, and the layout resolve picks for every wsize and tau.
 // tests/test_refine_layouts.py builds and runs it and compares the printed "accepted:" line with the
 // configs that have a bit-exact GPU case (tests/refine_configs.py).
+// With arguments "CONFIG:WSIZE:TAU" it prints, per argument, what a scene of that wsize and tau runs when
+// that number is asked for: "CONFIG WSIZE TAU -> RESOLVED GRID_DIV" (a number that names no layout is
+// asked as 1206, as pmvs_scene_create reads PMVS_REFINE_CONFIG); the same test maps its GPU cases to the
+// kernels they launch with it.
 #include "pmvs_refine_layouts.h"
 
 #include <climits>
 #include <cstdio>
+#include <cstdlib>
 
 using namespace pmvsdev;
 
@@ -123,10 +128,36 @@ static void test_resolve() {
       }
 }
 
-int main() {
+// "CONFIG:WSIZE:TAU" -> one line; false for anything else, or a wsize or tau no scene has
+static bool print_resolved(const char* arg) {
+  char* end = nullptr;
+  long v[3] = {0, 0, 0};
+  for (int i = 0; i < 3; ++i) {
+    v[i] = strtol(arg, &end, 10);
+    if (end == arg || *end != (i < 2 ? ':' : '\0') || v[i] < 0 || v[i] > 999999) return false;
+    arg = end + 1;
+  }
+  const int config = (int)v[0], wsize = (int)v[1], tau = (int)v[2];
+  if ((wsize != 5 && wsize != 7 && wsize != 9) || tau < 1 || tau > 16) return false;
+  RefineLayout asked = kWaveDefault;
+  (void)parse(config, asked);
+  const RefineLayout got = resolve(asked, wsize, tau);
+  printf("%d %d %d -> %d %d\n", config, wsize, tau, got.config, got.grid_div);
+  return true;
+}
+
+int main(int argc, char** argv) {
   test_parse();
   test_resolve();
   if (g_fail) return 1;
+  if (argc > 1) {
+    for (int i = 1; i < argc; ++i)
+      if (!print_resolved(argv[i])) {
+        fprintf(stderr, "refine_layouts_test: bad triple '%s' (CONFIG:WSIZE:TAU, wsize 5/7/9, tau 1-16)\n", argv[i]);
+        return 2;
+      }
+    return 0;
+  }
   // the accepted set as the table itself lists it (not kAccepted): every number below 400000 that parses
   printf("accepted:");
   RefineLayout l;

@@ -35,6 +35,10 @@ CONFIGS = {
                                   opts=dict(sequence=3, max_angle_deg=25.0, threshold=0.6),
                                   vis="ring2"),
     "min4_thr08": dict(views=10, w=400, h=300, level=1, opts=dict(min_image_num=4, threshold=0.8)),
+    # tau = min(2 * minImageNum, views) above 8: image selection, set_scales, the expand and filter stages
+    # and the seed phase with more than 8 images per patch (views `arc` degrees apart)
+    "min7_v16": dict(views=16, w=320, h=240, level=1, arc=6.0, opts=dict(min_image_num=7)),
+    "min5_v9_w5": dict(views=9, w=320, h=240, level=1, arc=8.0, opts=dict(min_image_num=5, wsize=5)),
     # photometrically hard scenes (per-view gain/bias, sensor noise, low-texture regions, an occluder):
     # final NCCs spread over ~0.6-1 and image selection / filterOutside decisions sit near their thresholds
     "hard_level0": dict(views=10, w=400, h=300, level=0, hard=True),
@@ -50,7 +54,8 @@ HARD_NEAR_MIN = {"hard_level0": {"constraint_near": 20, "gains_near": 2},
 def build(cfg):
     import pmvs_amd as P
     inp, p = P.synth_scene(cfg["views"], cfg["w"], cfg["h"], level=cfg["level"], num_targets=cfg.get("targets"),
-                           supersample=2, hard=cfg.get("hard", False), **cfg.get("opts", {}))
+                           supersample=2, hard=cfg.get("hard", False), arc_step_deg=cfg.get("arc"),
+                           **cfg.get("opts", {}))
     V = cfg["views"]
     if cfg.get("masks"):
         inp.masks = blob_masks(V, cfg["h"], cfg["w"], 1, keep=0.9)
@@ -124,6 +129,13 @@ def test_grab_and_my_f_matrix(pair):
     fg, _ = g.incc_eval(eq)
     fo = o.incc_eval(eq)
     assert np.array_equal(bits(fg), bits(fo)), name
+    tau = min(2 * inp.min_image_num, V)
+    if tau > 6:  # my_f over as many images as a patch of this scene holds
+        eq = eval_queries(V, cands, per=3, nimg=min(tau, V))
+        fg, _ = g.incc_eval(eq)
+        fo = o.incc_eval(eq)
+        assert (fo < 2.0).any(), name  # some query has enough valid textures for a value
+        assert np.array_equal(bits(fg), bits(fo)), (name, tau)
 
 
 def test_empty_and_invalid_batches(gpu_available):
@@ -147,7 +159,7 @@ def test_empty_and_invalid_batches(gpu_available):
 def test_full_loop_matrix(gpu_available, oracle_mod, name):
     """The whole expand/filter loop (pmvs_run_loop, CFindMatch::run after the seeds) under every
     option configuration above -- masks, edges, bimages, visdata, timages subsets, sequence,
-    maxAngle, csize 1/4, wsize 5/9, levels 0-2, minImageNum 2/4 -- equals the oracle's loop
+    maxAngle, csize 1/4, wsize 5/9, levels 0-2, minImageNum 2/4/5/7 -- equals the oracle's loop
     patch for patch (wave 128, min_candidates 256)."""
     import pmvs_amd as P
     inp, p = build(CONFIGS[name])

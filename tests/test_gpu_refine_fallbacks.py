@@ -2,7 +2,9 @@
 entry, pmvs_refine_batch: a split-form layout at wsize 9 runs the wavefront form 1206, and a wavefront
 layout with fewer texture slots than tau runs 2408 on half the grid.  Records and the six counters
 against the CPU oracle, as in test_gpu_parity.py::test_refine_configs_bit_exact.  (The lane form's
-choice of lanes per texture at tau <= 8 is what every small batch of the other tests runs.)"""
+choice of lanes per texture at tau <= 8 is what every small batch of the other tests runs; above tau = 8,
+where it takes 4 lanes per texture, and every other form above tau = 8 and at wsize 5 and 9:
+test_gpu_refine_envelope.py.)"""
 import pytest
 
 from conftest import small_scene

@@ -75,6 +75,7 @@ def test_seed_run_batch_invariance(gpu_available, monkeypatch, lookahead, near):
 def test_seed_matrix(gpu_available, cfg):
     inp, p = build(CONFIGS[cfg])
     g, o, pts, sg, stg, so, sto = run_pair(inp, batch=512)
+    assert len(so) > 0, cfg
     same_seeds(sg, so)
     assert [stg[k] for k in ("trial", "pass", "fail0", "fail1")] == [sto[k] for k in ("trial", "pass", "fail0", "fail1")]
     g.close()
