@@ -1003,6 +1003,86 @@ void oracle_distances(void* h, float* out) {
     for (int j = 0; j < s.num; ++j) out[(size_t)i * s.num + j] = d[i][j];
 }
 
+// ---- filter / expansion cell decisions, pinned to the reference's own filter.cpp / expand.cpp compiled
+// in oracle/_ref/filter (tests/test_filter_pinning.py).  The patch set: coords4[4 * i] and (image, ix, iy)
+// triples lists3[3 * off[i] .. 3 * off[i + 1]), added to an empty organizer in order (add_patch_p).
+static void pin_patch_set(int n, const float* coords4, const int* off, const int* lists3, std::vector<FPatch>& P) {
+  P.assign((size_t)n, FPatch());
+  for (int i = 0; i < n; ++i) {
+    for (int k = 0; k < 4; ++k) P[i].coord[k] = coords4[4 * i + k];
+    for (int e = off[i]; e < off[i + 1]; ++e) {
+      P[i].images.push_back(lists3[3 * e]);
+      P[i].grids.push_back({lists3[3 * e + 1], lists3[3 * e + 2]});
+    }
+  }
+}
+
+// set_dm_vgrids(o, P, 0) (filter_oracle.h, CFilter::setDepthMapsVGridsVPGridsAddPatchV(0)) at depth 0.
+// winners / depths: every target's cells, concatenated (patch or -1; depth_of the winner or 0);
+// collected[0] = count, then the collectPatches order; vcount[i] and vlists3 (capacity 3 * n * tnum ints):
+// every patch's vimages / vgrids as (image, ix, iy), concatenated; vpcount[cell] and vprows (capacity
+// n * tnum): the vpgrids cell lists, concatenated.
+void oracle_filter_depth_maps(void* h, int n, const float* coords4, const int* off, const int* lists3, int* winners,
+                              float* depths, int* collected, int* vcount, int* vlists3, int* vpcount, int* vprows) {
+  OScene& s = *static_cast<OScene*>(h);
+  const int saved = s.depth;
+  s.depth = 0;
+  std::vector<FPatch> P;
+  pin_patch_set(n, coords4, off, lists3, P);
+  Organizer o(s);
+  for (int p = 0; p < n; ++p) add_patch_p(o, P, p);
+  set_dm_vgrids(o, P, 0);
+  size_t c = 0, v = 0, r = 0;
+  for (int t = 0; t < s.tnum; ++t)
+    for (size_t i = 0; i < o.dpgrids[t].size(); ++i, ++c) {
+      const int d = o.dpgrids[t][i];
+      winners[c] = d;
+      depths[c] = d < 0 ? 0.0f : depth_of(s, t, P[d].coord);
+      vpcount[c] = (int)o.vpgrids[t][i].size();
+      for (int p : o.vpgrids[t][i]) vprows[r++] = p;
+    }
+  collected[0] = (int)o.ppatches.size();
+  for (size_t i = 0; i < o.ppatches.size(); ++i) collected[1 + i] = o.ppatches[i];
+  for (int i = 0; i < n; ++i) {
+    vcount[i] = (int)P[i].vimages.size();
+    for (size_t k = 0; k < P[i].vimages.size(); ++k) {
+      vlists3[v++] = P[i].vimages[k];
+      vlists3[v++] = P[i].vgrids[k].first;
+      vlists3[v++] = P[i].vgrids[k].second;
+    }
+  }
+  s.depth = saved;
+}
+
+// A sequence of check_counts / update_counts calls (expand_oracle.h, CExpand::checkCounts / updateCounts)
+// on a model whose pgrids hold the patch set and whose counts start at 0.  Call c: kinds[c] (0 check,
+// 1 update), candidate images / grids ilists3[3 * ioff[c] ..) and vimages / vgrids vlists3[3 * voff[c] ..).
+// rets[c]: the return value; counts_out: every target's cells, concatenated.
+void oracle_counts_seq(void* h, int n, const float* coords4, const int* off, const int* lists3, int depth, int cthr,
+                       int k, const int* kinds, const int* ioff, const int* ilists3, const int* voff,
+                       const int* vlists3, int* rets, int* counts_out) {
+  const OScene& s = *static_cast<const OScene*>(h);
+  std::vector<FPatch> P;
+  pin_patch_set(n, coords4, off, lists3, P);
+  Model m(s);
+  for (int p = 0; p < n; ++p) add_patch_p(m.o, P, p);
+  for (int c = 0; c < k; ++c) {
+    FPatch q;
+    for (int e = ioff[c]; e < ioff[c + 1]; ++e) {
+      q.images.push_back(ilists3[3 * e]);
+      q.grids.push_back({ilists3[3 * e + 1], ilists3[3 * e + 2]});
+    }
+    for (int e = voff[c]; e < voff[c + 1]; ++e) {
+      q.vimages.push_back(vlists3[3 * e]);
+      q.vgrids.push_back({vlists3[3 * e + 1], vlists3[3 * e + 2]});
+    }
+    rets[c] = kinds[c] == 0 ? check_counts(m, q, cthr, depth) : update_counts(m, q, cthr);
+  }
+  size_t c = 0;
+  for (int t = 0; t < s.tnum; ++t)
+    for (unsigned char v : m.counts[t]) counts_out[c++] = v;
+}
+
 // 1 when a result list exceeded PMVS_MAX_IMAGES since the last reset (see list_len).
 int oracle_list_overflow(int reset) {
   const int v = g_list_overflow.load();

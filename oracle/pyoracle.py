@@ -70,6 +70,8 @@ def lib():
         L.oracle_is_visible0.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.oracle_check_angles.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_void_p]
         L.oracle_distances.argtypes = [C.c_void_p, C.c_void_p]
+        L.oracle_filter_depth_maps.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10
+        L.oracle_counts_seq.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 7
         _lib = L
     return _lib
 
@@ -225,6 +227,91 @@ def ref_organizer(projections, widths, heights, num_targets, level, csize, ops):
     return res
 
 
+def _triples(lists):
+    """Lists of (image, ix, iy) -> (offsets [n + 1] int32, flat int32 [sum, 3])."""
+    off = np.zeros(len(lists) + 1, np.int32)
+    off[1:] = np.cumsum([len(l) for l in lists])
+    flat = np.zeros((max(int(off[-1]), 1), 3), np.int32)
+    if off[-1]:
+        flat[:off[-1]] = np.concatenate([np.asarray(l, np.int32).reshape(-1, 3) for l in lists if len(l)])
+    return off, flat
+
+
+def _triples_bytes(l):
+    a = np.asarray(l, np.int32).reshape(-1, 3)
+    return np.int32(len(a)).tobytes() + a.tobytes()
+
+
+def ref_filter(projections, widths, heights, num_targets, level, csize, min_image_num, coords, lists, ops):
+    """The reference's own CFilter / CExpand (oracle/_ref/filter, built from filter.cpp, expand.cpp,
+    findMatch.cpp, patchOrganizerS.cpp, photoSetS.cpp, camera.cpp and patch.cpp unmodified) on a scene
+    given as for ref_organizer and a patch set (coords [n, 4], per patch a list of (image, ix, iy)) added
+    through CPatchOrganizerS::addPatch in row order; `ops` and the results as in OracleScene.filter_ops.
+    Returns None when _ref is absent."""
+    import struct
+    import subprocess
+    import tempfile
+    exe = os.path.join(HERE, "_ref", "filter")
+    if not os.path.exists(exe):
+        return None
+    V, L = np.asarray(widths).shape
+    coords = np.ascontiguousarray(coords, np.float32)
+    n = len(coords)
+    out = bytearray(struct.pack("5i", V, num_targets, level, csize, L))
+    with tempfile.TemporaryDirectory() as d:
+        for v in range(V):
+            path = os.path.join(d, "%08d.txt" % v)
+            with open(path, "w") as f:
+                f.write("CONTOUR\n")
+                for row in projections[v]:
+                    f.write(" ".join(repr(float(x)) for x in row) + "\n")
+            b = path.encode()
+            out += struct.pack("i", len(b)) + b
+            out += np.asarray(widths[v], np.int32).tobytes() + np.asarray(heights[v], np.int32).tobytes()
+        out += struct.pack("i", n)
+        for c, l in zip(coords, lists):
+            out += c.tobytes() + _triples_bytes(l)
+        for op in ops:
+            if op[0] == "depth_maps":
+                out += struct.pack("i", 1)
+            elif op[0] == "counts":
+                _, depth, cthr, calls = op
+                out += struct.pack("5i", 2, depth, cthr, min_image_num, len(calls))
+                for kind, il, vl in calls:
+                    out += struct.pack("i", kind) + _triples_bytes(il) + _triples_bytes(vl)
+            else:
+                raise ValueError(op[0])
+        r = subprocess.run([exe], input=bytes(out), capture_output=True, check=True).stdout
+    cells = int(sum(((int(widths[t][level]) + csize - 1) // csize) * ((int(heights[t][level]) + csize - 1) // csize)
+                    for t in range(num_targets)))
+    pos, res = 0, []
+
+    def take(k, dt=np.int32):
+        nonlocal pos
+        a = np.frombuffer(r, dt, k, pos).copy()
+        pos += 4 * k
+        return a
+    for op in ops:
+        if op[0] == "depth_maps":
+            g = {"winner": take(cells), "depth": take(cells, np.float32)}
+            g["collected"] = take(int(take(1)[0]))
+            vcount, vl = np.zeros(n, np.int32), []
+            for i in range(n):
+                vcount[i] = take(1)[0]
+                vl.append(take(3 * int(vcount[i])))
+            g["vcount"], g["vlists"] = vcount, np.concatenate(vl + [np.zeros(0, np.int32)]).reshape(-1, 3)
+            vpcount, vp = np.zeros(cells, np.int32), []
+            for i in range(cells):
+                vpcount[i] = take(1)[0]
+                vp.append(take(int(vpcount[i])))
+            g["vpcount"], g["vprows"] = vpcount, np.concatenate(vp + [np.zeros(0, np.int32)])
+            res.append(g)
+        else:
+            res.append({"ret": take(len(op[3])), "counts": take(cells)})
+    assert pos == len(r), (pos, len(r))
+    return res
+
+
 def _check_lists():
     """The oracle never truncates a list: a result list longer than PMVS_MAX_IMAGES is an error."""
     if lib().oracle_list_overflow(1):
@@ -293,6 +380,49 @@ class OracleScene:
                 out = np.zeros((V, V), np.float32)
                 L.oracle_distances(self.h, _p(out))
                 res.append(out)
+        return res
+
+    def filter_ops(self, coords, lists, ops):
+        """The restatement's filter / expansion cell decisions on a patch set (coords [n, 4], per patch a
+        list of (image, ix, iy)) added to an empty organizer in row order, on the same op list as ref_filter:
+          ("depth_maps",)  set_dm_vgrids(additive 0) at depth 0 -> dict: winner [cells] (row or -1) and depth
+                           [cells] (f32, 0 where empty) over every target's cells concatenated; collected (the
+                           collectPatches order); vcount [n] and vlists [sum, 3] (every row's vimages /
+                           vgrids); vpcount [cells] and vprows [sum] (the vpgrids cell lists)
+          ("counts", depth, countThreshold1, calls)  calls = [(kind, images3, vimages3)], kind 0 check_counts,
+                           1 update_counts, on counts that start at 0 -> dict: ret [k], counts [cells]
+        minImageNum is the scene's."""
+        L = lib()
+        coords = np.ascontiguousarray(coords, np.float32)
+        n = len(coords)
+        off, flat = _triples(lists)
+        gw, gh = self.grid_sizes()
+        T = self.inputs.num_targets
+        cells = int(sum(int(gw[t]) * int(gh[t]) for t in range(T)))
+        res = []
+        for op in ops:
+            if op[0] == "depth_maps":
+                g = {"winner": np.zeros(cells, np.int32), "depth": np.zeros(cells, np.float32)}
+                collected = np.zeros(n + 1, np.int32)
+                vcount, vlists = np.zeros(n, np.int32), np.zeros((max(n * T, 1), 3), np.int32)
+                vpcount, vprows = np.zeros(cells, np.int32), np.zeros(max(n * T, 1), np.int32)
+                L.oracle_filter_depth_maps(self.h, n, _p(coords), _p(off), _p(flat), _p(g["winner"]), _p(g["depth"]),
+                                           _p(collected), _p(vcount), _p(vlists), _p(vpcount), _p(vprows))
+                g["collected"] = collected[1:1 + collected[0]].copy()
+                g["vcount"], g["vlists"] = vcount, vlists[:vcount.sum()].copy()
+                g["vpcount"], g["vprows"] = vpcount, vprows[:vpcount.sum()].copy()
+                res.append(g)
+            elif op[0] == "counts":
+                _, depth, cthr, calls = op
+                kinds = np.array([c[0] for c in calls], np.int32)
+                ioff, iflat = _triples([c[1] for c in calls])
+                voff, vflat = _triples([c[2] for c in calls])
+                g = {"ret": np.zeros(len(calls), np.int32), "counts": np.zeros(cells, np.int32)}
+                L.oracle_counts_seq(self.h, n, _p(coords), _p(off), _p(flat), depth, cthr, len(calls), _p(kinds),
+                                    _p(ioff), _p(iflat), _p(voff), _p(vflat), _p(g["ret"]), _p(g["counts"]))
+                res.append(g)
+            else:
+                raise ValueError(op[0])
         return res
 
     def level_sizes(self, levels):

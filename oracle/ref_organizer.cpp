@@ -13,8 +13,9 @@
 //   op 6  CPhotoSetS::setDistances           photoSetS.cpp:195-234
 //   also  CPatchOrganizerS::init             patchOrganizerS.cpp:50-82 (the cell grids every op uses)
 //
-// No CFindMatch can be constructed here: its COptim / CSeed / CExpand / CFilter members live in TUs
-// that need nlopt, CImg and Eigen, and so does CPhoto's constructor (its CImage base, image.cpp).
+// No CFindMatch can be constructed here: its COptim member lives in optim.cpp, which needs nlopt
+// (CSeed, CExpand and CFilter are buildable but not part of this program; ref_filter.cpp constructs the
+// last two), and CPhoto's constructor needs its CImage base (image.cpp, CImg).
 // Those symbols stay unresolved (non-PIE, --unresolved-symbols=ignore-all) and are never called; no
 // stand-in is written for any of them.  Instead the members the functions above read are
 // materialised in raw storage of the classes' sizes, each by its own (reference) constructor or

@@ -10,7 +10,9 @@ renderer regenerates them bit-for-bit).  Expected outputs come from two sources:
     samples on every pyramid level; the candidate centres of CExpand::findEmptyBlocks
     (expand.cpp:176-177 evaluated with the reference headers, expand_dirs.npz); the Harris and
     DoG feature points of every golden view (harris.cpp / dog.cpp, features.npz); the seed
-    phase's setF / computeEPD / triangulation of feature pairs (seeds.npz) -- these vectors are
+    phase's setF / computeEPD / triangulation of feature pairs (seeds.npz); the depth-map winners,
+    visible-image lists and _vpgrids of CFilter::setDepthMapsVGridsVPGridsAddPatchV and the answers of
+    CExpand::checkCounts / updateCounts (oracle/_ref/filter, filter_pin.npz) -- these vectors are
     REFERENCE outputs;
   * oracle/liboracle.so (the CPU restatement, pinned on the pieces above): pyramid CRCs,
     grabTex textures, my_f values, full preProcess->refinePatch->postProcess records and the
@@ -352,6 +354,325 @@ def make_organizer():
           f"depth cells set {(g['ref3'] >= 0).sum()}, visible {g['ref4'][:, 0].sum()}/{len(coords)}")
 
 
+FILTER_PIN = dict(views=6, width=320, height=240, level=1, num_targets=4, crop=(1, 300, 200), n_cand=2600, seed=41,
+                  copies=48, count_ops=((1, 4, 360), (2, 2, 360)))
+
+
+def filter_pin_scene():
+    """6 views at 320 x 240, level 1, 4 targets, target 1 cropped to 300 x 200 as in
+    tests/test_gpu_depth_maps.py: the targets' cell grids differ in size (80 x 60, 75 x 50, 80 x 60, 80 x 60)."""
+    c = FILTER_PIN
+    inp, p = P.synth_scene(c["views"], c["width"], c["height"], level=c["level"], num_targets=c["num_targets"],
+                           supersample=2)
+    t, w, h = c["crop"]
+    inp.images[t] = np.ascontiguousarray(inp.images[t][:h, :w])
+    return inp, p
+
+
+def filter_pin_patches(o, inp, p):
+    """The patch set of the filter pins, as PATCH_DTYPE records, the (original, copy) row pairs and the
+    number of leading rows that are a plain model (refined patches, outliers, fixed rows):
+    oracle-refined patches of the scene; the outliers of tests/test_gpu_filter.make_patch_set (copies
+    pushed 25 dscale towards their reference camera); a few fixed rows; rows far outside every image and
+    rows on the images' border cells (their lists point at arbitrary in-grid cells: addPatch takes the
+    lists as given); and, last, exact copies of rows that win depth-map cells -- depth ties far apart in
+    the array."""
+    c = FILTER_PIN
+    rng = np.random.default_rng(c["seed"])
+    cands = P.synth_candidates(p, inp.projections, c["n_cand"], seed=c["seed"])
+    pa = P.patches_from_refined(o.refine_batch(cands, nthreads=8)[0])
+    src = pa[rng.choice(len(pa), max(1, len(pa) // 50), replace=False)].copy()
+    for q in src:
+        cam = np.asarray(inp.projections[int(q["images"][0])], np.float64)
+        d = -np.linalg.solve(cam[:, :3], cam[:, 3]) - q["coord"][:3].astype(np.float64)
+        d /= np.linalg.norm(d)
+        q["coord"][:3] = (q["coord"][:3] + d * 25.0 * q["dscale"]).astype(np.float32)
+        q["ncc"] = np.float32(inp.threshold + 0.02)
+    pa = np.concatenate([pa, src])
+    pa["fix"][rng.random(len(pa)) < 0.01] = 1
+    gw, gh = o.grid_sizes()
+    far = pa[rng.choice(len(pa), 60, replace=False)].copy()
+    far["coord"][:40, :3] = rng.uniform(-1.6, 1.6, (40, 3)).astype(np.float32)  # many leave the images
+    far["coord"][40:43, :3] = [(0, 0, 50), (50, 0, 0), (0, -50, 0)]
+    # points whose projection into a target falls on a first or last column / row of its cells: a surface
+    # point is moved along the image's x or y direction in space, bisecting on the oracle's isVisible0
+    # (depth 0: "inside the grid") until the last position inside
+    edge = pa[rng.choice(len(pa), 64, replace=False)].copy()
+    for i, q in enumerate(edge):
+        t, axis, sign = i % inp.num_targets, (i // inp.num_targets) % 2, 1 - 2 * ((i // (2 * inp.num_targets)) % 2)
+        step = np.linalg.pinv(np.asarray(inp.projections[t], np.float64)[:, :3])[:, axis]
+        step *= sign / np.linalg.norm(step)
+        x0 = q["coord"].astype(np.float64)
+
+        def at(a):
+            x = x0.copy()
+            x[:3] += a * step
+            return x.astype(np.float32)
+
+        def inside(a):
+            return bool(o.organizer_ops([("vis0", at(a)[None], [t])])[0][0, 0])
+        lo, hi = 0.0, 4.0
+        if not inside(lo) or inside(hi):
+            continue
+        for _ in range(40):
+            mid = 0.5 * (lo + hi)
+            lo, hi = (mid, hi) if inside(mid) else (lo, mid)
+        q["coord"] = at(lo)
+    n_plain = len(pa)
+    crafted = np.concatenate([far[:43], edge])
+    for q in crafted:  # arbitrary in-grid cells of one or two targets, plus a non-target image
+        k = int(rng.integers(1, 3))
+        ts = rng.permutation(inp.num_targets)[:k]
+        q["num_images"] = k + 1
+        q["images"][:k] = ts
+        q["grids"][:k, 0] = [rng.integers(0, gw[t]) for t in ts]
+        q["grids"][:k, 1] = [rng.integers(0, gh[t]) for t in ts]
+        q["images"][k] = inp.num_targets + int(rng.integers(0, len(inp.images) - inp.num_targets))
+        q["grids"][k] = (3, 3)
+        q["fix"] = 0
+    pa = np.concatenate([pa, crafted])
+    coords, lists = filter_pin_lists(pa)
+    win = np.unique(o.filter_ops(coords, lists, [("depth_maps",)])[0]["winner"])
+    orig = rng.permutation(win[(win >= 0) & (win < len(pa) // 2)])[:c["copies"]]
+    orig.sort()
+    pairs = np.stack([orig, len(pa) + np.arange(len(orig))], 1).astype(np.int32)
+    return np.concatenate([pa, pa[orig]]), pairs, n_plain
+
+
+def filter_pin_lists(pa):
+    """PATCH_DTYPE records -> (coords [n, 4], per row its (image, ix, iy) list)."""
+    lists = []
+    for q in pa:
+        k = int(q["num_images"])
+        lists.append(np.concatenate([q["images"][:k, None].astype(np.int32), q["grids"][:k].astype(np.int32)], 1))
+    return np.ascontiguousarray(pa["coord"], np.float32), lists
+
+
+def filter_pin_count_calls(rng, lists, gw, gh, V, tnum, depth, k):
+    """A sequence of (kind, images3, vimages3) calls for checkCounts (kind 0) / updateCounts (kind 1):
+    candidates with 0-4 cells taken from a pool of three unoccupied cells per target (so their counts climb
+    through the threshold as the updates accumulate) and 0-2 occupied cells, sometimes an image >= tnum,
+    sometimes a cell outside the grid; vimages in the remaining targets.  Every eighth call is the same
+    probe check, whose answer the earlier updates change."""
+    occ = [[] for _ in range(tnum)]
+    for l in lists:
+        for t, ix, iy in l:
+            if t < tnum:
+                occ[t].append((int(ix), int(iy)))
+    pool = []
+    for t in range(tnum):
+        taken, cells = set(occ[t]), []
+        while len(cells) < 3:
+            c = (int(rng.integers(0, gw[t])), int(rng.integers(0, gh[t])))
+            if c not in taken:
+                taken.add(c)
+                cells.append(c)
+        pool.append(cells)
+    ne = 3 if depth <= 1 else 2
+    probe = [(t,) + pool[t][0] for t in range(ne)] + [(tnum - 1,) + occ[tnum - 1][0]]
+    calls = []
+    for c in range(k):
+        if c % 8 == 7:
+            calls.append((0, probe, []))
+            continue
+        e, f = int(rng.integers(0, 5)), int(rng.integers(0, 3))
+        ts = rng.permutation(tnum).tolist()
+        il = [(t,) + pool[t][int(rng.integers(0, 3))] for t in ts[:e]]
+        il += [(t,) + occ[t][int(rng.integers(0, len(occ[t])))] for t in ts[e:e + f]]
+        rest = ts[e + f:]
+        if rest and rng.random() < 0.25:  # a cell outside the grid
+            t = rest.pop()
+            il.append((t,) + [(-1, 2), (int(gw[t]), 2), (2, -1), (2, int(gh[t]))][int(rng.integers(0, 4))])
+        if rng.random() < 0.3:
+            il.append((int(rng.integers(tnum, V)), int(rng.integers(0, 40)), int(rng.integers(0, 40))))
+        il = [il[i] for i in rng.permutation(len(il))]
+        vl = []
+        for t in rest:
+            r = rng.random()
+            if r < 0.5:
+                vl.append((t,) + pool[t][int(rng.integers(0, 3))])
+            elif r < 0.6:
+                vl.append((t, int(gw[t]), int(gh[t])))
+        calls.append((int(rng.random() < 0.4), il, vl))
+    return calls
+
+
+def filter_pin_coverage(g):
+    """The edges the filter pins need, asserted from the fixture's inputs and the REFERENCE's outputs."""
+    tnum, min_num = int(g["params"][5]), int(g["params"][9])
+    n = len(g["coords"])
+    off = g["list_off"]
+    # ---- depth maps
+    win, pairs = g["ref_dm_winner"], g["copies"]
+    assert len(g["ref_dm_collected"]) == n and len(np.unique(g["ref_dm_collected"])) == n  # every row is in a target cell
+    assert not np.array_equal(g["ref_dm_collected"], np.arange(n))  # collectPatches' order is its own
+    assert len(pairs) >= 40 and (pairs[:, 1] - pairs[:, 0]).min() > n // 3
+    assert all(np.array_equal(g["coords"][a], g["coords"][b]) for a, b in pairs)
+    assert np.isin(pairs[:, 0], win).sum() >= 40 and not np.isin(pairs[:, 1], win).any()  # ties: the earlier row
+    filled = win >= 0
+    assert filled.sum() >= 1000 and len(np.unique(win[filled])) >= 100 and (~filled).any()
+    assert not g["ref_dm_depth"][~filled].view(np.uint32).any()
+    vrow = np.repeat(np.arange(n), g["ref_dm_vcount"])
+    listed = np.zeros((n, tnum), bool)
+    for i in range(n):
+        t = g["lists"][off[i]:off[i + 1], 0]
+        listed[i, t[t < tnum]] = True
+    assert not listed[vrow, g["ref_dm_vlists"][:, 0]].any()  # vimages are the targets not in images
+    # rows outside every grid they are not listed in; none of them wins a cell (their lists are arbitrary)
+    outside = np.flatnonzero((g["ref_dm_vcount"] == 0) & (listed.sum(1) <= 2))
+    assert len(outside) >= 3 and (~np.isin(outside, win)).sum() >= 3
+    gw, gh = g["grid_dims"][:, 0], g["grid_dims"][:, 1]
+    vl = g["ref_dm_vlists"]
+    assert ((vl[:, 1] == gw[vl[:, 0]] - 1) | (vl[:, 2] == gh[vl[:, 0]] - 1)).sum() >= 5  # border cells
+    assert ((vl[:, 1] == 0) | (vl[:, 2] == 0)).any()
+    assert g["ref_dm_vpcount"].sum() == len(vl) and g["ref_dm_vpcount"].max() >= 2
+    # ---- counts: replay the bookkeeping the calls imply (counts only ever grow by one per touched cell)
+    cell0 = np.concatenate([[0], np.cumsum(gw[:tnum].astype(np.int64) * gh[:tnum])])
+    occupied = np.zeros(cell0[-1], bool)
+    lt = g["lists"]
+    m = lt[:, 0] < tnum
+    occupied[cell0[lt[m, 0]] + lt[m, 2].astype(np.int64) * gw[lt[m, 0]] + lt[m, 1]] = True
+    depths = set()
+    for j in range(int(g["count_ops"])):
+        depth, cthr = (int(x) for x in g[f"c{j}_params"])
+        depths.add(depth <= 1)
+        kinds, ret = g[f"c{j}_kinds"], g[f"c{j}_ret"]
+        ioff, il, voff, vl = g[f"c{j}_ioff"], g[f"c{j}_ilists"], g[f"c{j}_voff"], g[f"c{j}_vlists"]
+        counts = np.zeros(cell0[-1], np.int64)
+        seen_empty, seen_full0, at, oob, nontarget, probes = set(), False, set(), False, False, {}
+        for c in range(len(kinds)):
+            full = empty = 0
+            entries = [tuple(x) for x in il[ioff[c]:ioff[c + 1]]]
+            ventries = [tuple(x) for x in vl[voff[c]:voff[c + 1]]] if kinds[c] else []
+            for t, ix, iy in entries + ventries:
+                if t >= tnum:
+                    nontarget = True
+                    continue
+                if not (0 <= ix < gw[t] and 0 <= iy < gh[t]):
+                    oob = True
+                    continue
+                i = cell0[t] + iy * gw[t] + ix
+                if kinds[c] == 0 and occupied[i]:
+                    full += 1
+                    continue
+                at.add(int(counts[i]))
+                if cthr <= counts[i]:
+                    full += 1
+                else:
+                    empty += 1
+                if kinds[c]:
+                    counts[i] += 1
+            if kinds[c] == 0:
+                if full:
+                    seen_empty.add(empty)
+                else:
+                    seen_full0 = True
+                probes.setdefault((tuple(entries),), set()).add(int(ret[c]))
+        assert np.array_equal(counts, g[f"c{j}_counts"]) and counts.max() < 255
+        edge = min_num if depth <= 1 else min_num - 1
+        assert {edge - 1, edge} <= seen_empty and {min_num - 2, min_num - 1, min_num} <= seen_empty and seen_full0
+        assert {cthr - 1, cthr} <= at and oob and nontarget
+        for kind in (0, 1):
+            assert set(ret[kinds == kind].tolist()) == {0, 1}, (j, kind)
+        assert any(len(v) == 2 for v in probes.values())  # earlier updates change a later answer
+    assert depths == {True, False}
+
+
+def save_npz(path, g):
+    """np.savez_compressed with fixed member dates, so a second run writes the same bytes."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k, v in g.items():
+            b = io.BytesIO()
+            np.lib.format.write_array(b, np.asanyarray(v), allow_pickle=False)
+            zi = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_DEFLATED
+            zi.external_attr = 0o644 << 16
+            z.writestr(zi, b.getvalue())
+
+
+def filter_pin_ops(g):
+    """The op list of OracleScene.filter_ops / pyoracle.ref_filter that the fixture's inputs describe."""
+    ops = [("depth_maps",)]
+    for j in range(int(g["count_ops"])):
+        depth, cthr = (int(x) for x in g[f"c{j}_params"])
+        ioff, il, voff, vl = g[f"c{j}_ioff"], g[f"c{j}_ilists"], g[f"c{j}_voff"], g[f"c{j}_vlists"]
+        calls = [(int(g[f"c{j}_kinds"][c]), il[ioff[c]:ioff[c + 1]], vl[voff[c]:voff[c + 1]])
+                 for c in range(len(ioff) - 1)]
+        ops.append(("counts", depth, cthr, calls))
+    return ops
+
+
+def filter_pin_inputs(g):
+    off = g["list_off"]
+    return g["coords"], [g["lists"][off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+
+def filter_pin_records(g):
+    """The fixture's patch set as PATCH_DTYPE records (empty vimages)."""
+    coords, lists = filter_pin_inputs(g)
+    pa = np.zeros(len(coords), P.PATCH_DTYPE)
+    pa["coord"] = coords
+    for f in ("normal", "ncc", "dscale", "ascale", "timages", "fix"):
+        pa[f] = g[f]
+    for q, l in zip(pa, lists):
+        q["num_images"] = len(l)
+        q["images"][:len(l)] = l[:, 0]
+        q["grids"][:len(l)] = l[:, 1:]
+    return pa
+
+
+def make_filter():
+    """CFilter::setDepthMapsVGridsVPGridsAddPatchV(0) (depth-map winners, visible-image lists, _vpgrids)
+    and CExpand::checkCounts / updateCounts of the reference's own filter.cpp / expand.cpp
+    (oracle/_ref/filter) on the filter-pin patch set: inputs and REFERENCE outputs only (filter_pin.npz)."""
+    c = FILTER_PIN
+    inp, p = filter_pin_scene()
+    o = O.OracleScene(inp)
+    maxlv = inp.level + 3
+    w, h = o.level_sizes(maxlv)
+    gw, gh = o.grid_sizes()
+    pa, pairs, n_plain = filter_pin_patches(o, inp, p)
+    coords, lists = filter_pin_lists(pa)
+    off = np.zeros(len(lists) + 1, np.int64)
+    off[1:] = np.cumsum([len(l) for l in lists])
+    t, cw, ch = c["crop"]
+    g = {"params": np.array([c["views"], c["width"], c["height"], inp.level, inp.csize, inp.num_targets, t, cw, ch,
+                             inp.min_image_num, n_plain], np.int64),
+         "widths": w, "heights": h, "grid_dims": np.stack([gw, gh], 1).astype(np.int32),
+         "coords": coords, "normal": pa["normal"], "ncc": pa["ncc"], "dscale": pa["dscale"],
+         "ascale": pa["ascale"], "timages": pa["timages"].astype(np.int16), "fix": pa["fix"].astype(np.int8), "list_off": off, "lists": np.concatenate(lists).astype(np.int16),
+         "copies": pairs, "count_ops": np.int64(len(c["count_ops"]))}
+    rng = np.random.default_rng(c["seed"] + 1)
+    for j, (depth, cthr, k) in enumerate(c["count_ops"]):
+        calls = filter_pin_count_calls(rng, lists, gw, gh, len(inp.images), inp.num_targets, depth, k)
+        g[f"c{j}_params"] = np.array([depth, cthr], np.int32)
+        g[f"c{j}_kinds"] = np.array([x[0] for x in calls], np.int8)
+        for name, col in (("i", 1), ("v", 2)):
+            lo = np.zeros(len(calls) + 1, np.int32)
+            lo[1:] = np.cumsum([len(x[col]) for x in calls])
+            g[f"c{j}_{name}off"] = lo
+            g[f"c{j}_{name}lists"] = np.array([e for x in calls for e in x[col]], np.int16).reshape(-1, 3)
+    ops = filter_pin_ops(g)
+    ref = O.ref_filter(inp.projections, w, h, inp.num_targets, inp.level, inp.csize, inp.min_image_num, coords, lists,
+                       ops)
+    o.close()
+    if ref is None:
+        raise SystemExit("oracle/_ref/filter not built (reference absent)")
+    for k, v in ref[0].items():
+        g["ref_dm_" + k] = v
+    for j in range(len(c["count_ops"])):
+        g[f"c{j}_ret"] = ref[1 + j]["ret"].astype(np.int8)
+        g[f"c{j}_counts"] = ref[1 + j]["counts"].astype(np.uint8)
+    filter_pin_coverage(g)
+    path = os.path.join(HERE, "filter_pin.npz")
+    save_npz(path, g)
+    win = g["ref_dm_winner"]
+    print(f"{path}: {os.path.getsize(path)} B, {len(coords)} patches, {(win >= 0).sum()} of {len(win)} cells filled by "
+          f"{len(np.unique(win[win >= 0]))} winners, {len(g['ref_dm_vlists'])} vimages")
+
+
 def make(name, views, width, height, level, csize, ntex, neval, nref):
     inp, p = P.synth_scene(views, width, height, level=level, csize=csize, supersample=2)
     o = O.OracleScene(inp)
@@ -400,6 +721,7 @@ if __name__ == "__main__":
             globals()["make_" + name]()
         raise SystemExit(0)
     make_organizer()
+    make_filter()
     make_isneighbor()
     make_expand_dirs()
     make_features()

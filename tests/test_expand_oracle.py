@@ -1,7 +1,8 @@
 """CPU checks of the expansion oracle (oracle/expand_oracle.h, a restatement of
-PMVS3::CExpand::run, expand.cpp:17-406).  Parity unpinned against the reference binary (its
-expansion needs the whole findMatch runtime, unbuildable here): these are the invariants the
-reference's own bookkeeping implies, on a synthetic ring."""
+PMVS3::CExpand::run, expand.cpp:17-406).  expand.cpp itself compiles here, and checkCounts /
+updateCounts are pinned to its object code (tests/test_filter_pinning.py); a whole run is not, because
+expandSub and computeRadius call into optim.cpp (nlopt).  These are the invariants the reference's own
+bookkeeping implies, on a synthetic ring."""
 import numpy as np
 import pytest
 
