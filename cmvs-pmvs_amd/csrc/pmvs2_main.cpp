@@ -1,4 +1,4 @@
-// pmvs2_main.cpp -- the `pmvs2 prefix option_file [PATCH] [PSET] [DEPTH] [PIXDEPTH]` executable (reference
+// pmvs2_main.cpp -- the `pmvs2 prefix option_file [PATCH] [PSET] [DEPTH] [PIXDEPTH] [FUSE]` executable (reference
 // source/pmvs.cpp:7-63 with CFindMatch::init / run / write, findMatch.cpp:30-224), driving the
 // MI355X-native core through its C-ABI (include/pmvs_amd.h).  A drop-in for the program
 // genOption's pmvs.sh calls (genOption.cpp:73): same arguments, same input tree
@@ -126,7 +126,7 @@ void usage(const char* argv0) {
             << "oimages  5  0 2 4 6 8 (enumeration)" << std::endl
             << "        -1  24 48 (range specification)" << std::endl
             << std::endl
-            << "[Optional export] PATCH PSET DEPTH PIXDEPTH" << std::endl
+            << "[Optional export] PATCH PSET DEPTH PIXDEPTH FUSE" << std::endl
             << " i.e export patch and pset: prefix option_file PATCH PSET"
             << " i.e export patch only: prefix option_file PATCH" << std::endl
             << " DEPTH: every target image's depth map, one value per csize x csize cell, as" << std::endl
@@ -134,7 +134,11 @@ void usage(const char* argv0) {
             << " PIXDEPTH: every target image's depth map, one value per pixel at the option's level, every" << std::endl
             << "        patch rendered as a plane element of radius csize (at most " << PMVS_PIXEL_MAX_RADIUS
             << ") pixels, as" << std::endl
-            << "        models/option_file.pixdepth.<8-digit image number>.pfm (0 = no patch)" << std::endl;
+            << "        models/option_file.pixdepth.<8-digit image number>.pfm (0 = no patch)" << std::endl
+            << " FUSE: the per-pixel maps of all target images (radius csize) fused into one point cloud: a pixel" << std::endl
+            << "        whose surface point at least 2 other target images see at a depth within 1 % and with a" << std::endl
+            << "        normal within 60 degrees gives one oriented, coloured point, once per surface point, as the" << std::endl
+            << "        binary PLY models/option_file.fused.ply (x y z nx ny nz, colour, support)" << std::endl;
 }
 
 }  // namespace
@@ -147,12 +151,13 @@ int main(int argc, char* argv[]) {
   for (int i = 0; i < argc; ++i) std::cout << std::endl << argv[i];
   std::cout << std::endl;
   const std::string prefix = argv[1], option = argv[2];
-  bool export_patch = false, export_pset = false, export_depth = false, export_pixdepth = false;
+  bool export_patch = false, export_pset = false, export_depth = false, export_pixdepth = false, export_fuse = false;
   for (int i = 3; i < argc; ++i) {
     if (std::string(argv[i]) == "PATCH") export_patch = true;
     if (std::string(argv[i]) == "PSET") export_pset = true;
     if (std::string(argv[i]) == "DEPTH") export_depth = true;
     if (std::string(argv[i]) == "PIXDEPTH") export_pixdepth = true;
+    if (std::string(argv[i]) == "FUSE") export_fuse = true;
   }
   const double t0 = now_s();
 
@@ -452,6 +457,29 @@ int main(int argc, char* argv[]) {
       std::snprintf(name, sizeof(name), ".pixdepth.%08d.pfm", images[t]);
       CHECK("pfm", pmvs_write_pfm((out + name).c_str(), dims[0], dims[1], depth.data()));
     }
+  }
+  if (export_fuse) {
+    // the model just written fused over all target images (pmvs_loop_fuse, writer order): a counting
+    // call sizes the host arrays
+    pmvs_fuse_params fp{};
+    fp.radius = std::min<int>(opt->csize, PMVS_PIXEL_MAX_RADIUS);
+    fp.min_support = 2;
+    fp.depth_rel = 0.01f;
+    fp.normal_cos = 0.5f;
+    pmvs_fuse_buffers fb{};
+    int64_t npts = 0;
+    CHECK("fuse", pmvs_loop_fuse(sc, PMVS_EXPORT_WRITER_ORDER, 0, tnum, &fp, 0, &fb, &npts));
+    const size_t cap = (size_t)std::max<int64_t>(npts, 1);
+    std::vector<float> coord(cap * 3), normal(cap * 3);
+    std::vector<uint8_t> color(cap * 3), support(cap);
+    fb.coord = coord.data();
+    fb.normal = normal.data();
+    fb.color = color.data();
+    fb.support = support.data();
+    int64_t written = 0;
+    CHECK("fuse", pmvs_loop_fuse(sc, PMVS_EXPORT_WRITER_ORDER, 0, tnum, &fp, npts, &fb, &written));
+    CHECK("fused ply", pmvs_write_ply_binary((out + ".fused.ply").c_str(), std::min(npts, written), coord.data(),
+                                             normal.data(), color.data(), support.data()));
   }
   pmvs_scene_destroy(sc);
   pmvs_options_free(opt);

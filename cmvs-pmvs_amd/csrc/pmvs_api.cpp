@@ -1725,6 +1725,89 @@ pmvs_status pmvs_pixel_maps_patches(pmvs_scene* sc, const pmvs_patch* patches, i
   return pixel_maps_records(sc, dP, n, flags, first_target, num_targets, radius, buffers);
 }
 
+// ---- fusion of the per-pixel maps (pmvs_fuse.hip)
+namespace {
+const pmvs_depthmap_buffers kNoMaps{};  // pixel_args_ok wants a buffers pointer; the fusion's maps are scratch
+
+bool fuse_args_ok(const pmvs_scene* sc, int32_t flags, int32_t first, int32_t num, const pmvs_fuse_params* p, int64_t cap,
+                  const pmvs_fuse_buffers* b, const int64_t* count) {
+  return p && b && count && cap >= 0 && pixel_args_ok(sc, flags, first, num, p->radius, &kNoMaps) && p->min_support >= 0 &&
+         p->min_support <= 255 && std::isfinite(p->depth_rel) && p->depth_rel >= 0.0f && !std::isnan(p->normal_cos);
+}
+
+// The fusion of the device records dP[0, n).
+pmvs_status fuse_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, int32_t flags, int32_t first, int32_t num,
+                         const pmvs_fuse_params* prm, int64_t cap, const pmvs_fuse_buffers* b, int64_t* count) {
+  const bool dev = (flags & PMVS_EXPORT_DEVICE) != 0;
+  const size_t pixels = (size_t)pixel_map_layout(sc, first, num, nullptr, nullptr);
+  static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "fusion array types");
+  ExportTemp tmp;
+  int* d_src = nullptr;
+  if ((flags & PMVS_EXPORT_WRITER_ORDER) && n > 0) {  // the export's order, from the export's code
+    EXPCHK(tmp.alloc(&d_src, (size_t)n));
+    EXPCHK(export_order(sc->ds, dP, n, depth_map_layout(sc, nullptr, nullptr), d_src, nullptr, nullptr, sc->stream));
+  }
+  // no more points than pixels can be emitted: the staging is sized by that, whatever the caller's cap
+  const size_t pts = (size_t)std::min<int64_t>(cap, (int64_t)pixels);
+  FuseArrays a;
+  if (dev) {  // straight into the caller's device buffers
+    a.support_map = b->support_map; a.coord = b->coord; a.normal = b->normal; a.color = b->color; a.support = b->support;
+    a.pixel = (long long*)b->pixel; a.patch = b->patch;
+  } else {    // device staging for the requested arrays
+    if (b->support_map) EXPCHK(tmp.alloc(&a.support_map, pixels));
+    if (b->coord && pts) EXPCHK(tmp.alloc(&a.coord, pts * 3));
+    if (b->normal && pts) EXPCHK(tmp.alloc(&a.normal, pts * 3));
+    if (b->color && pts) EXPCHK(tmp.alloc(&a.color, pts * 3));
+    if (b->support && pts) EXPCHK(tmp.alloc(&a.support, pts));
+    if (b->pixel && pts) EXPCHK(tmp.alloc(&a.pixel, pts));
+    if (b->patch && pts) EXPCHK(tmp.alloc(&a.patch, pts));
+  }
+  long long total = 0;
+  EXPCHK(fuse_pass(sc->ds, sc->hviews.data(), dP, n, d_src, first, num, *prm, (long long)pts, a, &total, sc->stream));
+  *count = total;
+  if (!dev) {
+    const size_t w = (size_t)std::min<long long>(total, (long long)cap);  // the points written
+    auto down = [&](void* dst, const void* src, size_t bytes) {
+      return (dst && src && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sc->stream) : hipSuccess;
+    };
+    EXPCHK(down(b->support_map, a.support_map, pixels));
+    EXPCHK(down(b->coord, a.coord, w * 3 * sizeof(float)));
+    EXPCHK(down(b->normal, a.normal, w * 3 * sizeof(float)));
+    EXPCHK(down(b->color, a.color, w * 3));
+    EXPCHK(down(b->support, a.support, w));
+    EXPCHK(down(b->pixel, a.pixel, w * sizeof(int64_t)));
+    EXPCHK(down(b->patch, a.patch, w * sizeof(int32_t)));
+    EXPCHK(hipStreamSynchronize(sc->stream));
+  }
+  return PMVS_OK;
+}
+}  // namespace
+
+pmvs_status pmvs_loop_fuse(pmvs_scene* sc, int32_t flags, int32_t first_target, int32_t num_targets,
+                           const pmvs_fuse_params* params, int64_t cap, const pmvs_fuse_buffers* buffers, int64_t* count) {
+  if (!fuse_args_ok(sc, flags, first_target, num_targets, params, cap, buffers, count)) return fail(PMVS_EINVAL, "invalid argument");
+  if (sc->lkept < 0) return fail(PMVS_EINVAL, "loop_fuse: no loop result on the device");
+  HIPCHK(hipSetDevice(sc->device));
+  return fuse_records(sc, sc->fpatches.p, sc->lkept, flags, first_target, num_targets, params, cap, buffers, count);
+}
+
+pmvs_status pmvs_fuse_patches(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, int32_t flags, int32_t first_target,
+                              int32_t num_targets, const pmvs_fuse_params* params, int64_t cap, const pmvs_fuse_buffers* buffers,
+                              int64_t* count) {
+  if (!fuse_args_ok(sc, flags, first_target, num_targets, params, cap, buffers, count) || n < 0 || (n > 0 && !patches))
+    return fail(PMVS_EINVAL, "invalid argument");
+  if (pmvs_status st = check_export_patches(sc, patches, n, nullptr)) return st;
+  HIPCHK(hipSetDevice(sc->device));
+  // a buffer of its own: sc->fpatches may hold a loop result
+  ExportTemp tmp;
+  pmvs_patch* dP = nullptr;
+  if (n) {
+    EXPCHK(tmp.alloc(&dP, (size_t)n));
+    EXPCHK(hipMemcpyAsync(dP, patches, (size_t)n * sizeof(pmvs_patch), hipMemcpyHostToDevice, sc->stream));
+  }
+  return fuse_records(sc, dP, n, flags, first_target, num_targets, params, cap, buffers, count);
+}
+
 // ---- text files (pmvs_text.hip)
 namespace {
 bool text_args_ok(const pmvs_scene* sc, int32_t kind, int32_t flags, const char* out, int64_t cap, const int64_t* bytes) {

@@ -676,4 +676,35 @@ pmvs_status pmvs_write_pfm(const char* path, int32_t width, int32_t height, cons
   return ofstr.good() ? PMVS_OK : pmvs_io_fail(PMVS_EINVAL, "write failed: %s", path);
 }
 
+// A fused point cloud (pmvs_loop_fuse) as binary little-endian PLY: 28-byte records.
+pmvs_status pmvs_write_ply_binary(const char* path, int64_t n, const float* coord, const float* normal,
+                                  const uint8_t* color, const uint8_t* support) {
+  if (!path || n < 0 || (n > 0 && (!coord || !normal || !color || !support))) return pmvs_io_fail(PMVS_EINVAL, "invalid argument");
+  std::ofstream ofstr(path, std::ios::binary);
+  if (!ofstr.is_open()) return pmvs_io_fail(PMVS_EINVAL, "cannot write %s", path);
+  ofstr << "ply\nformat binary_little_endian 1.0\nelement vertex " << n
+        << "\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\n"
+           "property float nz\nproperty uchar diffuse_red\nproperty uchar diffuse_green\nproperty uchar diffuse_blue\n"
+           "property uchar support\nend_header\n";
+  constexpr int64_t kChunk = 4096;  // records per write
+  std::vector<char> buf((size_t)(kChunk * 28));
+  for (int64_t p0 = 0; p0 < n; p0 += kChunk) {
+    const int64_t m = std::min<int64_t>(kChunk, n - p0);
+    for (int64_t i = 0; i < m; ++i) {
+      char* rec = buf.data() + 28 * i;
+      const float f[6] = {coord[3 * (p0 + i)],  coord[3 * (p0 + i) + 1],  coord[3 * (p0 + i) + 2],
+                          normal[3 * (p0 + i)], normal[3 * (p0 + i) + 1], normal[3 * (p0 + i) + 2]};
+      for (int k = 0; k < 6; ++k) {
+        uint32_t u;
+        std::memcpy(&u, f + k, 4);
+        for (int j = 0; j < 4; ++j) rec[4 * k + j] = (char)((u >> (8 * j)) & 0xff);
+      }
+      rec[24] = (char)color[3 * (p0 + i)], rec[25] = (char)color[3 * (p0 + i) + 1], rec[26] = (char)color[3 * (p0 + i) + 2];
+      rec[27] = (char)support[p0 + i];
+    }
+    ofstr.write(buf.data(), (std::streamsize)(28 * m));
+  }
+  return ofstr.good() ? PMVS_OK : pmvs_io_fail(PMVS_EINVAL, "write failed: %s", path);
+}
+
 }  // extern "C"

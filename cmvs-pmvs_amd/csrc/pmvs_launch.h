@@ -165,6 +165,22 @@ hipError_t depth_map_pack(const pmvs_patch* P, const int* src, int n, float4* co
 hipError_t pixel_map_pass(const DScene& s, const DView* hviews, const pmvs_patch* P, int n, const int* src, int first,
                           int count, int radius, const DepthMapArrays& out, hipStream_t st);
 
+// ---- fusion of the per-pixel maps (pmvs_fuse.hip; the definition is csrc/pmvs_fuse.h)
+// Device pointers of the arrays of pmvs_fuse_buffers (include/pmvs_amd.h); null = not wanted.
+struct FuseArrays {
+  unsigned char* support_map = nullptr;
+  float *coord = nullptr, *normal = nullptr;
+  unsigned char *color = nullptr, *support = nullptr;
+  long long* pixel = nullptr;
+  int* patch = nullptr;
+};
+// The fusion of targets [first, first + count) over the records P[0, n) (rows as pixel_map_pass takes
+// them): the support map and the first min(*total, cap) points into `out`, *total = the points emitted.
+// Returns after the stream has finished the work; its scratch (30 bytes per pixel of the range and the
+// maps' own) is freed by then.
+hipError_t fuse_pass(const DScene& s, const DView* hviews, const pmvs_patch* P, int n, const int* src, int first, int count,
+                     const pmvs_fuse_params& prm, long long cap, const FuseArrays& out, long long* total, hipStream_t st);
+
 // ---- filter pass (pmvs_filter.hip)
 // The fields of a patch that neighbour and visibility tests read from OTHER patches (isNeighbor,
 // computeGain, isVisible), one 64-B line per patch instead of 2-3 lines of its 1.6-KB record;

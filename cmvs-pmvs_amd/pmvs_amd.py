@@ -121,6 +121,14 @@ class DepthMapBuffers(C.Structure):  # pmvs_depthmap_buffers
     _fields_ = [(k, C.c_void_p) for k in ("patch", "depth", "normal", "ncc")]
 
 
+class FuseParams(C.Structure):  # pmvs_fuse_params
+    _fields_ = [("radius", C.c_int32), ("min_support", C.c_int32), ("depth_rel", C.c_float), ("normal_cos", C.c_float)]
+
+
+class FuseBuffers(C.Structure):  # pmvs_fuse_buffers
+    _fields_ = [(k, C.c_void_p) for k in ("support_map", "coord", "normal", "color", "support", "pixel", "patch")]
+
+
 class SeedStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("trial", "pass_", "fail0", "fail1", "refined", "rounds", "candidates",
                                           "reserved")] + [(k, C.c_double) for k in ("wall_ms", "gen_ms", "refine_ms")]
@@ -166,6 +174,7 @@ EXPORTS = ["pmvs_last_error", "pmvs_device_count", "pmvs_scene_create", "pmvs_sc
            "pmvs_loop_export_sizes", "pmvs_loop_export", "pmvs_export_patches_sizes", "pmvs_export_patches",
            "pmvs_depth_map_layout", "pmvs_loop_depth_maps", "pmvs_depth_maps_patches", "pmvs_write_pfm",
            "pmvs_pixel_map_layout", "pmvs_loop_pixel_maps", "pmvs_pixel_maps_patches",
+           "pmvs_loop_fuse", "pmvs_fuse_patches", "pmvs_write_ply_binary",
            "pmvs_loop_text", "pmvs_text_patches", "pmvs_selftest_format", "pmvs_selftest_labels",
            "pmvs_scene_set_shard", "pmvs_scene_set_shard_rccl", "pmvs_scene_set_cluster",
            "pmvs_scene_set_cluster_rccl", "pmvs_rccl_unique_id",
@@ -246,6 +255,11 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.pmvs_loop_pixel_maps.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DepthMapBuffers)]
     lib.pmvs_pixel_maps_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                             C.POINTER(DepthMapBuffers)]
+    lib.pmvs_loop_fuse.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(FuseParams), C.c_int64,
+                                   C.POINTER(FuseBuffers), C.POINTER(C.c_int64)]
+    lib.pmvs_fuse_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(FuseParams),
+                                      C.c_int64, C.POINTER(FuseBuffers), C.POINTER(C.c_int64)]
+    lib.pmvs_write_ply_binary.argtypes = [C.c_char_p, C.c_int64] + [C.c_void_p] * 4
     lib.pmvs_loop_text.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                    C.POINTER(C.c_int64)]
     lib.pmvs_text_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -723,6 +737,58 @@ class Scene:
         return self._pixel_map_call(lambda *a: self.lib.pmvs_pixel_maps_patches(self.handle, _ptr(pa), len(pa), *a),
                                     writer_order, device, arrays, first_target, num_targets, radius)
 
+    # pmvs_fuse_buffers: array name -> (dtype, shape from (pixels of the range, points))
+    FUSE_ARRAYS = {"support_map": ("uint8", lambda px, n: (px,)), "coord": ("float32", lambda px, n: (n, 3)),
+                   "normal": ("float32", lambda px, n: (n, 3)), "color": ("uint8", lambda px, n: (n, 3)),
+                   "support": ("uint8", lambda px, n: (n,)), "pixel": ("int64", lambda px, n: (n,)),
+                   "patch": ("int32", lambda px, n: (n,))}
+
+    def _fuse_call(self, call, writer_order, device, arrays, first_target, num_targets, radius, min_support, depth_rel,
+                   normal_cos):
+        num = self.desc.num_targets - first_target if num_targets is None else num_targets
+        prm = FuseParams(self.desc.csize if radius is None else radius, min_support, depth_rel, normal_cos)
+        flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
+        count = C.c_int64(0)
+        _check(call(flags, first_target, num, C.byref(prm), 0, C.byref(FuseBuffers()), C.byref(count)))  # the counting call
+        pixels, n = int(self.pixel_map_layout(first_target, num)[1][-1]), int(count.value)
+        names = list(self.FUSE_ARRAYS) if arrays is None else list(arrays)
+        out, buf = {}, FuseBuffers()
+        for k in names:
+            dt, shape = self.FUSE_ARRAYS[k]
+            if device:
+                import torch
+                out[k] = torch.empty(shape(pixels, n), dtype=getattr(torch, dt), device=torch.device("cuda", self.device))
+                setattr(buf, k, out[k].data_ptr() if out[k].numel() else None)
+            else:
+                out[k] = np.empty(shape(pixels, n), dt)
+                setattr(buf, k, out[k].ctypes.data if out[k].size else None)
+        _check(call(flags, first_target, num, C.byref(prm), n, C.byref(buf), C.byref(count)))
+        if int(count.value) != n:
+            raise PmvsError(f"the fusion emitted {count.value} points after counting {n}")
+        return out
+
+    def loop_fuse(self, writer_order: bool = True, device: bool = False, arrays=None, first_target: int = 0, num_targets=None,
+                  radius=None, min_support: int = 2, depth_rel: float = 0.01, normal_cos: float = 0.5) -> dict:
+        """pmvs_loop_fuse: the per-pixel maps of the last run_loop(fetch=False) result over targets
+        [first_target, first_target + num_targets) (None: all from first_target on) fused into one point
+        cloud, keyed by the fields of pmvs_fuse_buffers: support_map [pixels] uint8 (how many other
+        targets of the range see each pixel's surface point consistently), and per emitted point coord
+        [n, 3], normal [n, 3], color [n, 3] uint8, support [n] uint8, pixel [n] int64 (its index in
+        pixel_map_layout() of the range), patch [n] int32.  The arrays are sized by a counting call
+        first.  radius None: csize.  A range is fused as if the scene had no other targets, so it is
+        not a slice of the full call.  Does not consume the result.  device=True: torch tensors on the
+        scene's device, written there.  arrays: the names wanted (None = all)."""
+        return self._fuse_call(lambda *a: self.lib.pmvs_loop_fuse(self.handle, *a), writer_order, device, arrays,
+                               first_target, num_targets, radius, min_support, depth_rel, normal_cos)
+
+    def fuse_patches(self, patches: np.ndarray, writer_order: bool = True, device: bool = False, arrays=None,
+                     first_target: int = 0, num_targets=None, radius=None, min_support: int = 2, depth_rel: float = 0.01,
+                     normal_cos: float = 0.5) -> dict:
+        """pmvs_fuse_patches: loop_fuse's arrays for caller-supplied PATCH_DTYPE records."""
+        pa = np.ascontiguousarray(patches, PATCH_DTYPE)
+        return self._fuse_call(lambda *a: self.lib.pmvs_fuse_patches(self.handle, _ptr(pa), len(pa), *a), writer_order,
+                               device, arrays, first_target, num_targets, radius, min_support, depth_rel, normal_cos)
+
     def _text(self, call, device: bool, out):
         """A size query, the buffer (numpy uint8, or a torch uint8 tensor on the scene's device; `out`
         supplies it) and the call that fills it; returns the buffer cut to the text's size."""
@@ -933,6 +999,18 @@ def write_ply(path: str, fields, colors):
     f = np.ascontiguousarray(fields, np.float32).reshape(-1, 11)
     c = np.ascontiguousarray(colors, np.int32).reshape(-1, 3)
     _check(load_library().pmvs_write_ply(path.encode(), len(f), _ptr(f), _ptr(c)))
+
+
+def write_ply_binary(path: str, coord, normal, color, support):
+    """pmvs_write_ply_binary: a fused point cloud (Scene.loop_fuse's coord, normal, color, support) as one
+    binary little-endian PLY of 28-byte vertices."""
+    c = np.ascontiguousarray(coord, np.float32).reshape(-1, 3)
+    nm = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+    col = np.ascontiguousarray(color, np.uint8).reshape(-1, 3)
+    sup = np.ascontiguousarray(support, np.uint8).reshape(-1)
+    if not len(c) == len(nm) == len(col) == len(sup):
+        raise ValueError("write_ply_binary takes arrays of one length")
+    _check(load_library().pmvs_write_ply_binary(path.encode(), len(c), _ptr(c), _ptr(nm), _ptr(col), _ptr(sup)))
 
 
 def write_pfm(path: str, data):

@@ -454,6 +454,82 @@ pmvs_status pmvs_pixel_maps_patches(pmvs_scene* scene, const pmvs_patch* patches
                                     int32_t first_target, int32_t num_targets, int32_t radius,
                                     const pmvs_depthmap_buffers* buffers);
 
+/* The per-pixel maps fused into one dense, cross-view-checked point cloud on the device: per pixel the
+ * number of other targets that see the same surface point (the support map, the signal of
+ * view-dependent filtering), and one oriented, coloured point per supported pixel, emitted once per
+ * surface point and not once per view.  There is no reference for this; the definition below is the
+ * contract (csrc/pmvs_fuse.h implements it once, for host and device).  All f64 arithmetic is unfused,
+ * sums left to right, as for the maps.
+ * The fusion is over the targets of the range [first_target, first_target + num_targets) ONLY, as if the
+ * scene had no other targets: that bounds memory and makes a range call well defined.  A range call is
+ * therefore NOT a slice of the call over all targets: supports count fewer views and other pixels emit.
+ *  1. Maps: the patch, depth and normal maps of pmvs_loop_pixel_maps for the range, params->radius and
+ *     the flags (the same code renders them, so the same bytes).
+ *  2. The point of a filled pixel (t, u, v) with depth d: P and oaxis = view t's projection at the level
+ *     and its optical axis, f64 from f32; a = P0 - u*P2, b = P1 - v*P2, c3 = oaxis[0..2]; solve
+ *     [a3; b3; c3] S = (-a_w, -b_w, d - oaxis[3]) by Cramer's rule in the maps' operation order:
+ *     det = a3.(b3 x c3), S = ((-a_w)*(b3 x c3) + (-b_w)*(c3 x a3) + (d - oaxis3)*(a3 x b3)) / det;
+ *     Sf = (float)S.  The pixel is valid iff the three components of Sf are finite.
+ *  3. A valid pixel p = (t, u, v) is consistent with target s != t of the range iff, with
+ *     (x, y) = CCamera::project(view s, (Sf, 1.0f), level) and zs = OpticalAxis(s) * (Sf, 1.0f) in f32,
+ *     px = floor((double)x + 0.5), py likewise: q = (s, px, py) lies in [0, Ws) x [0, Hs) (compared in
+ *     double: a NaN fails, clamped values cannot wrap); q is filled; with ds the depth at q, zs > 0 and
+ *     fabs((double)ds - (double)zs) <= (double)depth_rel * (double)zs; and with n, m the normals stored at
+ *     p and q, (double)n0*m0 + (double)n1*m1 + (double)n2*m2 >= (double)normal_cos (no normalisation).
+ *  4. support(p) = the number of consistent s; 0 for empty or invalid pixels (at most 255: a byte).
+ *     pass(p) = filled and valid and support(p) >= min_support.
+ *  5. emit(p) = pass(p) and there is no s < t in the range with p consistent with s and pass(q(p, s)).
+ *     A suppressed pixel so has a passing consistent pixel in a lower target, and that chain ends at an
+ *     emitted one: no supported surface point is lost.  Nothing depends on the order of the work.
+ *  6. The points: the emitted pixels in ascending pixel index of the range (target, row, column); per
+ *     point coord = Sf, normal = the pixel's, color = the three bytes of pixel (u, v) of target t's image
+ *     at the scene's level as pmvs_scene_get_level returns them, support, pixel = its index in the layout
+ *     of pmvs_pixel_map_layout for the range, patch = the row.
+ * flags, rows, record validation and the use of the loop's result are those of the pixel-map calls.
+ * *count receives the number of emitted points, which may exceed cap; only the first min(*count, cap)
+ * points are written and nothing past cap; cap = 0 with NULL point arrays is the counting call.  With
+ * PMVS_EXPORT_DEVICE every pointer of the buffers is a device pointer on the scene's device.
+ * PMVS_EINVAL: a NULL scene, params, buffers or count; another flag bit; an empty range or one outside the
+ * scene's targets; a parameter outside the ranges below; cap < 0; no loop result.  PMVS_ENOMEM when the
+ * device cannot hold the scratch: 21 bytes per pixel of the RANGE (patch 4, depth 4, normal 12, support 1;
+ * the support map is the caller's when given in device mode), the pixel maps' own scratch, and 9 bytes per
+ * pixel for the pass flags and the compaction (and in host mode the requested arrays, for min(cap, pixels
+ * of the range) points: no more can be emitted, so a generous cap costs nothing).  All of it is
+ * allocated for the call and freed on return; the call returns after its work has finished. */
+typedef struct pmvs_fuse_params {
+  int32_t radius;       /* the maps' radius, 0..PMVS_PIXEL_MAX_RADIUS */
+  int32_t min_support;  /* 0..255: other targets of the range that must agree */
+  float   depth_rel;    /* finite, >= 0: relative depth tolerance */
+  float   normal_cos;   /* not NaN: least dot product of the two stored normals */
+} pmvs_fuse_params;
+
+typedef struct pmvs_fuse_buffers {   /* any pointer may be NULL: that array is skipped */
+  uint8_t* support_map;  /* pixels of the range */
+  float*   coord;        /* cap x 3 */
+  float*   normal;       /* cap x 3 */
+  uint8_t* color;        /* cap x 3 */
+  uint8_t* support;      /* cap */
+  int64_t* pixel;        /* cap */
+  int32_t* patch;        /* cap */
+} pmvs_fuse_buffers;
+
+/* Reads the result pmvs_run_loop left on the device where it lies and does not consume it (the digest of
+ * pmvs_loop_hash is the same before and after). */
+pmvs_status pmvs_loop_fuse(pmvs_scene* scene, int32_t flags, int32_t first_target, int32_t num_targets,
+                           const pmvs_fuse_params* params, int64_t cap, const pmvs_fuse_buffers* buffers,
+                           int64_t* count);
+/* The same for caller-supplied records, validated and uploaded as pmvs_pixel_maps_patches does.  n = 0 gives
+ * a zero support map and *count = 0. */
+pmvs_status pmvs_fuse_patches(pmvs_scene* scene, const pmvs_patch* patches, int32_t n, int32_t flags,
+                              int32_t first_target, int32_t num_targets, const pmvs_fuse_params* params,
+                              int64_t cap, const pmvs_fuse_buffers* buffers, int64_t* count);
+/* A point cloud as one binary PLY: the header `format binary_little_endian 1.0`, `element vertex n`,
+ * float x y z nx ny nz, uchar diffuse_red diffuse_green diffuse_blue, uchar support; then n 28-byte
+ * records.  Host arrays (coord and normal n x 3 floats, color n x 3 bytes, support n bytes).  PMVS_EINVAL
+ * for a NULL path, n < 0, a NULL array with n > 0, or a file that cannot be written. */
+pmvs_status pmvs_write_ply_binary(const char* path, int64_t n, const float* coord, const float* normal,
+                                  const uint8_t* color, const uint8_t* support);
+
 /* The .ply / .patch / .pset text of the model, formatted on the device: the bytes pmvs_write_ply /
  * pmvs_write_patches / pmvs_write_pset write from the export of the same records and flags
  * (CPatchOrganizerS::writePLY patchOrganizerS.cpp:687-776, writePatches2 :89-132 with Patch::operator<<
