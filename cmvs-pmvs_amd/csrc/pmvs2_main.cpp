@@ -1,4 +1,4 @@
-// pmvs2_main.cpp -- the `pmvs2 prefix option_file [PATCH] [PSET] [DEPTH] [PIXDEPTH] [FUSE]` executable (reference
+// pmvs2_main.cpp -- the `pmvs2 prefix option_file [PATCH] [PSET] [DEPTH] [PIXDEPTH] [FUSE] [MESH]` executable (reference
 // source/pmvs.cpp:7-63 with CFindMatch::init / run / write, findMatch.cpp:30-224), driving the
 // MI355X-native core through its C-ABI (include/pmvs_amd.h).  A drop-in for the program
 // genOption's pmvs.sh calls (genOption.cpp:73): same arguments, same input tree
@@ -126,7 +126,7 @@ void usage(const char* argv0) {
             << "oimages  5  0 2 4 6 8 (enumeration)" << std::endl
             << "        -1  24 48 (range specification)" << std::endl
             << std::endl
-            << "[Optional export] PATCH PSET DEPTH PIXDEPTH FUSE" << std::endl
+            << "[Optional export] PATCH PSET DEPTH PIXDEPTH FUSE MESH" << std::endl
             << " i.e export patch and pset: prefix option_file PATCH PSET"
             << " i.e export patch only: prefix option_file PATCH" << std::endl
             << " DEPTH: every target image's depth map, one value per csize x csize cell, as" << std::endl
@@ -138,7 +138,10 @@ void usage(const char* argv0) {
             << " FUSE: the per-pixel maps of all target images (radius csize) fused into one point cloud: a pixel" << std::endl
             << "        whose surface point at least 2 other target images see at a depth within 1 % and with a" << std::endl
             << "        normal within 60 degrees gives one oriented, coloured point, once per surface point, as the" << std::endl
-            << "        binary PLY models/option_file.fused.ply (x y z nx ny nz, colour, support)" << std::endl;
+            << "        binary PLY models/option_file.fused.ply (x y z nx ny nz, colour, support)" << std::endl
+            << " MESH: FUSE's maps integrated into a truncated signed distance volume (the fused cloud's bounding" << std::endl
+            << "        box padded by 3 voxels, voxel = its longest extent / 256, truncation 3 voxels) and meshed by" << std::endl
+            << "        naive surface nets, as the binary PLY models/option_file.mesh.ply (x y z nx ny nz, colour; faces)" << std::endl;
 }
 
 }  // namespace
@@ -151,13 +154,14 @@ int main(int argc, char* argv[]) {
   for (int i = 0; i < argc; ++i) std::cout << std::endl << argv[i];
   std::cout << std::endl;
   const std::string prefix = argv[1], option = argv[2];
-  bool export_patch = false, export_pset = false, export_depth = false, export_pixdepth = false, export_fuse = false;
+  bool export_patch = false, export_pset = false, export_depth = false, export_pixdepth = false, export_fuse = false, export_mesh = false;
   for (int i = 3; i < argc; ++i) {
     if (std::string(argv[i]) == "PATCH") export_patch = true;
     if (std::string(argv[i]) == "PSET") export_pset = true;
     if (std::string(argv[i]) == "DEPTH") export_depth = true;
     if (std::string(argv[i]) == "PIXDEPTH") export_pixdepth = true;
     if (std::string(argv[i]) == "FUSE") export_fuse = true;
+    if (std::string(argv[i]) == "MESH") export_mesh = true;
   }
   const double t0 = now_s();
 
@@ -458,7 +462,7 @@ int main(int argc, char* argv[]) {
       CHECK("pfm", pmvs_write_pfm((out + name).c_str(), dims[0], dims[1], depth.data()));
     }
   }
-  if (export_fuse) {
+  if (export_fuse || export_mesh) {
     // the model just written fused over all target images (pmvs_loop_fuse, writer order): a counting
     // call sizes the host arrays
     pmvs_fuse_params fp{};
@@ -478,8 +482,33 @@ int main(int argc, char* argv[]) {
     fb.support = support.data();
     int64_t written = 0;
     CHECK("fuse", pmvs_loop_fuse(sc, PMVS_EXPORT_WRITER_ORDER, 0, tnum, &fp, npts, &fb, &written));
-    CHECK("fused ply", pmvs_write_ply_binary((out + ".fused.ply").c_str(), std::min(npts, written), coord.data(),
-                                             normal.data(), color.data(), support.data()));
+    npts = std::min(npts, written);
+    if (export_fuse)
+      CHECK("fused ply", pmvs_write_ply_binary((out + ".fused.ply").c_str(), npts, coord.data(), normal.data(), color.data(),
+                                               support.data()));
+    if (export_mesh) {
+      // the same maps meshed in the cloud's padded bounding box (pmvs_loop_mesh); a cloud with no extent
+      // gives an empty mesh
+      int64_t nv = 0, nf = 0;
+      std::vector<float> vertex, vnormal;
+      std::vector<uint8_t> vcolor;
+      std::vector<int32_t> face;
+      pmvs_volume vol{};
+      if (npts > 0 && pmvs_volume_from_points(npts, coord.data(), 256, 3, &vol) == PMVS_OK) {
+        pmvs_tsdf_params tp{};
+        tp.fuse = fp;
+        tp.trunc = 3.0f * vol.voxel;
+        pmvs_mesh_buffers mb{};
+        CHECK("mesh", pmvs_loop_mesh(sc, PMVS_EXPORT_WRITER_ORDER, 0, tnum, &tp, &vol, 1, 0, 0, &mb, &nv, &nf));
+        vertex.resize((size_t)nv * 3), vnormal.resize((size_t)nv * 3), vcolor.resize((size_t)nv * 3), face.resize((size_t)nf * 3);
+        mb.vertex = vertex.data(), mb.normal = vnormal.data(), mb.color = vcolor.data(), mb.face = face.data();
+        int64_t wv = 0, wf = 0;
+        CHECK("mesh", pmvs_loop_mesh(sc, PMVS_EXPORT_WRITER_ORDER, 0, tnum, &tp, &vol, 1, nv, nf, &mb, &wv, &wf));
+        nv = std::min(nv, wv), nf = std::min(nf, wf);
+      }
+      CHECK("mesh ply", pmvs_write_ply_mesh_binary((out + ".mesh.ply").c_str(), nv, vertex.data(), vnormal.data(),
+                                                   vcolor.data(), nf, face.data()));
+    }
   }
   pmvs_scene_destroy(sc);
   pmvs_options_free(opt);

@@ -1808,6 +1808,215 @@ pmvs_status pmvs_fuse_patches(pmvs_scene* sc, const pmvs_patch* patches, int32_t
   return fuse_records(sc, dP, n, flags, first_target, num_targets, params, cap, buffers, count);
 }
 
+// ---- meshing of the fused maps (pmvs_mesh.hip)
+namespace {
+const pmvs_fuse_buffers kNoCloud{};  // fuse_args_ok wants buffers and a count; the meshing emits no cloud
+const int64_t kNoCount = 0;
+
+bool volume_ok(const pmvs_volume* v) {
+  if (!v || !std::isfinite(v->origin[0]) || !std::isfinite(v->origin[1]) || !std::isfinite(v->origin[2])) return false;
+  if (!std::isfinite(v->voxel) || !(v->voxel > 0.0f)) return false;
+  if (v->dims[0] < 1 || v->dims[1] < 1 || v->dims[2] < 1) return false;
+  return (int64_t)v->dims[0] * v->dims[1] <= INT32_MAX && (int64_t)v->dims[0] * v->dims[1] * v->dims[2] <= INT32_MAX;
+}
+
+bool tsdf_args_ok(const pmvs_scene* sc, int32_t flags, int32_t first, int32_t num, const pmvs_tsdf_params* p,
+                  const pmvs_volume* v) {
+  return p && fuse_args_ok(sc, flags, first, num, &p->fuse, 0, &kNoCloud, &kNoCount) && std::isfinite(p->trunc) &&
+         p->trunc > 0.0f && volume_ok(v);
+}
+
+bool mesh_args_ok(int32_t min_obs, int64_t vcap, int64_t fcap, const pmvs_mesh_buffers* b, const int64_t* nverts,
+                  const int64_t* nfaces) {
+  return b && nverts && nfaces && min_obs >= 1 && min_obs <= 255 && vcap >= 0 && fcap >= 0;
+}
+
+size_t volume_voxels(const pmvs_volume& v) { return (size_t)v.dims[0] * v.dims[1] * v.dims[2]; }
+
+// The fusion's maps and pass flags of the device records dP[0, n) into `f`, enqueued on the scene's stream.
+pmvs_status tsdf_maps(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, int32_t flags, int32_t first, int32_t num,
+                      const pmvs_fuse_params& prm, ExportTemp& tmp, FuseMaps& f) {
+  int* d_src = nullptr;
+  if ((flags & PMVS_EXPORT_WRITER_ORDER) && n > 0) {  // the export's order, from the export's code
+    EXPCHK(tmp.alloc(&d_src, (size_t)n));
+    EXPCHK(export_order(sc->ds, dP, n, depth_map_layout(sc, nullptr, nullptr), d_src, nullptr, nullptr, sc->stream));
+  }
+  EXPCHK(fuse_maps_pass(sc->ds, sc->hviews.data(), dP, n, d_src, first, num, prm, nullptr, f, sc->stream));
+  return PMVS_OK;
+}
+
+// The TSDF of the device records dP[0, n).
+pmvs_status tsdf_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, int32_t flags, int32_t first, int32_t num,
+                         const pmvs_tsdf_params* prm, const pmvs_volume* vol, const pmvs_tsdf_buffers* b) {
+  const bool dev = (flags & PMVS_EXPORT_DEVICE) != 0;
+  if (!b->tsdf && !b->obs && !b->color) return PMVS_OK;
+  const size_t voxels = volume_voxels(*vol);
+  ExportTemp tmp;
+  FuseMaps f;
+  TsdfArrays a;
+  if (dev) {  // straight into the caller's device buffers
+    a.tsdf = b->tsdf; a.obs = b->obs; a.color = b->color;
+  } else {    // device staging for the requested arrays
+    if (b->tsdf) EXPCHK(tmp.alloc(&a.tsdf, voxels));
+    if (b->obs) EXPCHK(tmp.alloc(&a.obs, voxels));
+    if (b->color) EXPCHK(tmp.alloc(&a.color, voxels * 4));
+  }
+  if (pmvs_status st = tsdf_maps(sc, dP, n, flags, first, num, prm->fuse, tmp, f)) return st;
+  EXPCHK(tsdf_integrate(sc->ds, f, first, num, *vol, prm->trunc, a, sc->stream));
+  if (!dev) {
+    auto down = [&](void* dst, const void* src, size_t bytes) {
+      return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sc->stream) : hipSuccess;
+    };
+    EXPCHK(down(b->tsdf, a.tsdf, voxels * sizeof(float)));
+    EXPCHK(down(b->obs, a.obs, voxels));
+    EXPCHK(down(b->color, a.color, voxels * 4));
+  }
+  EXPCHK(hipStreamSynchronize(sc->stream));  // the maps are freed on return
+  return PMVS_OK;
+}
+
+// Surface nets over device volume arrays into the caller's buffers (device mode) or through staging.
+pmvs_status mesh_device_volume(pmvs_scene* sc, bool dev, const pmvs_volume* vol, int32_t min_obs, const float* d_tsdf,
+                               const uint8_t* d_obs, const uint8_t* d_color, int64_t vcap, int64_t fcap,
+                               const pmvs_mesh_buffers* b, int64_t* nverts, int64_t* nfaces) {
+  const size_t voxels = volume_voxels(*vol);
+  const size_t cells = (size_t)(vol->dims[0] - 1) * (vol->dims[1] - 1) * (vol->dims[2] - 1);
+  // no more vertices than cells and no more faces than 6 per voxel exist: the staging is sized by that
+  const size_t nv = (size_t)std::min<int64_t>(vcap, (int64_t)cells), nf = (size_t)std::min<int64_t>(fcap, (int64_t)voxels * 6);
+  ExportTemp tmp;
+  MeshArrays a;
+  if (dev) {
+    a.vertex = b->vertex; a.normal = b->normal; a.color = b->color; a.face = b->face;
+  } else {
+    if (b->vertex && nv) EXPCHK(tmp.alloc(&a.vertex, nv * 3));
+    if (b->normal && nv) EXPCHK(tmp.alloc(&a.normal, nv * 3));
+    if (b->color && nv) EXPCHK(tmp.alloc(&a.color, nv * 3));
+    if (b->face && nf) EXPCHK(tmp.alloc(&a.face, nf * 3));
+  }
+  long long tv = 0, tf = 0;
+  EXPCHK(tsdf_mesh_pass(*vol, min_obs, d_tsdf, d_obs, d_color, (long long)nv, (long long)nf, a, &tv, &tf, sc->stream));
+  *nverts = tv;
+  *nfaces = tf;
+  if (!dev) {
+    const size_t wv = (size_t)std::min<long long>(tv, (long long)nv), wf = (size_t)std::min<long long>(tf, (long long)nf);
+    auto down = [&](void* dst, const void* src, size_t bytes) {
+      return (dst && src && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sc->stream) : hipSuccess;
+    };
+    EXPCHK(down(b->vertex, a.vertex, wv * 3 * sizeof(float)));
+    EXPCHK(down(b->normal, a.normal, wv * 3 * sizeof(float)));
+    EXPCHK(down(b->color, a.color, wv * 3));
+    EXPCHK(down(b->face, a.face, wf * 3 * sizeof(int32_t)));
+    EXPCHK(hipStreamSynchronize(sc->stream));
+  }
+  return PMVS_OK;
+}
+
+// Integration then extraction of the device records dP[0, n): the volume stays on the device.
+pmvs_status mesh_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, int32_t flags, int32_t first, int32_t num,
+                         const pmvs_tsdf_params* prm, const pmvs_volume* vol, int32_t min_obs, int64_t vcap, int64_t fcap,
+                         const pmvs_mesh_buffers* b, int64_t* nverts, int64_t* nfaces) {
+  const size_t voxels = volume_voxels(*vol);
+  ExportTemp tmp;
+  TsdfArrays a;
+  EXPCHK(tmp.alloc(&a.tsdf, voxels));
+  EXPCHK(tmp.alloc(&a.obs, voxels));
+  EXPCHK(tmp.alloc(&a.color, voxels * 4));
+  {
+    FuseMaps f;
+    if (pmvs_status st = tsdf_maps(sc, dP, n, flags, first, num, prm->fuse, tmp, f)) return st;
+    EXPCHK(tsdf_integrate(sc->ds, f, first, num, *vol, prm->trunc, a, sc->stream));
+    EXPCHK(hipStreamSynchronize(sc->stream));  // the maps are freed here, before the extraction's scratch
+  }
+  return mesh_device_volume(sc, (flags & PMVS_EXPORT_DEVICE) != 0, vol, min_obs, a.tsdf, a.obs, a.color, vcap, fcap, b, nverts,
+                            nfaces);
+}
+
+// The records of a _patches call on the device (a buffer of its own: sc->fpatches may hold a loop result).
+pmvs_status upload_records(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, ExportTemp& tmp, pmvs_patch** dP) {
+  *dP = nullptr;
+  if (n) {
+    EXPCHK(tmp.alloc(dP, (size_t)n));
+    EXPCHK(hipMemcpyAsync(*dP, patches, (size_t)n * sizeof(pmvs_patch), hipMemcpyHostToDevice, sc->stream));
+  }
+  return PMVS_OK;
+}
+}  // namespace
+
+pmvs_status pmvs_loop_tsdf(pmvs_scene* sc, int32_t flags, int32_t first_target, int32_t num_targets,
+                           const pmvs_tsdf_params* params, const pmvs_volume* volume, const pmvs_tsdf_buffers* buffers) {
+  if (!buffers || !tsdf_args_ok(sc, flags, first_target, num_targets, params, volume)) return fail(PMVS_EINVAL, "invalid argument");
+  if (sc->lkept < 0) return fail(PMVS_EINVAL, "loop_tsdf: no loop result on the device");
+  HIPCHK(hipSetDevice(sc->device));
+  return tsdf_records(sc, sc->fpatches.p, sc->lkept, flags, first_target, num_targets, params, volume, buffers);
+}
+
+pmvs_status pmvs_tsdf_patches(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, int32_t flags, int32_t first_target,
+                              int32_t num_targets, const pmvs_tsdf_params* params, const pmvs_volume* volume,
+                              const pmvs_tsdf_buffers* buffers) {
+  if (!buffers || !tsdf_args_ok(sc, flags, first_target, num_targets, params, volume) || n < 0 || (n > 0 && !patches))
+    return fail(PMVS_EINVAL, "invalid argument");
+  if (pmvs_status st = check_export_patches(sc, patches, n, nullptr)) return st;
+  HIPCHK(hipSetDevice(sc->device));
+  ExportTemp tmp;
+  pmvs_patch* dP = nullptr;
+  if (pmvs_status st = upload_records(sc, patches, n, tmp, &dP)) return st;
+  return tsdf_records(sc, dP, n, flags, first_target, num_targets, params, volume, buffers);
+}
+
+pmvs_status pmvs_tsdf_mesh(pmvs_scene* sc, int32_t flags, const pmvs_volume* volume, int32_t min_obs, const float* tsdf,
+                           const uint8_t* obs, const uint8_t* color, int64_t vcap, int64_t fcap, const pmvs_mesh_buffers* buffers,
+                           int64_t* nverts, int64_t* nfaces) {
+  if (!sc || (flags & ~PMVS_EXPORT_DEVICE) || !volume_ok(volume) || !tsdf || !obs ||
+      !mesh_args_ok(min_obs, vcap, fcap, buffers, nverts, nfaces))
+    return fail(PMVS_EINVAL, "invalid argument");
+  HIPCHK(hipSetDevice(sc->device));
+  const bool dev = (flags & PMVS_EXPORT_DEVICE) != 0;
+  ExportTemp tmp;
+  if (!dev) {  // the volume goes up
+    const size_t voxels = volume_voxels(*volume);
+    float* d_tsdf = nullptr;
+    uint8_t *d_obs = nullptr, *d_color = nullptr;
+    EXPCHK(tmp.alloc(&d_tsdf, voxels));
+    EXPCHK(tmp.alloc(&d_obs, voxels));
+    EXPCHK(hipMemcpyAsync(d_tsdf, tsdf, voxels * sizeof(float), hipMemcpyHostToDevice, sc->stream));
+    EXPCHK(hipMemcpyAsync(d_obs, obs, voxels, hipMemcpyHostToDevice, sc->stream));
+    if (color) {
+      EXPCHK(tmp.alloc(&d_color, voxels * 4));
+      EXPCHK(hipMemcpyAsync(d_color, color, voxels * 4, hipMemcpyHostToDevice, sc->stream));
+    }
+    tsdf = d_tsdf, obs = d_obs, color = d_color;
+  }
+  if (pmvs_status st = mesh_device_volume(sc, dev, volume, min_obs, tsdf, obs, color, vcap, fcap, buffers, nverts, nfaces)) return st;
+  if (!dev) EXPCHK(hipStreamSynchronize(sc->stream));  // the uploads too, when there were no cells
+  return PMVS_OK;
+}
+
+pmvs_status pmvs_loop_mesh(pmvs_scene* sc, int32_t flags, int32_t first_target, int32_t num_targets,
+                           const pmvs_tsdf_params* params, const pmvs_volume* volume, int32_t min_obs, int64_t vcap, int64_t fcap,
+                           const pmvs_mesh_buffers* buffers, int64_t* nverts, int64_t* nfaces) {
+  if (!tsdf_args_ok(sc, flags, first_target, num_targets, params, volume) ||
+      !mesh_args_ok(min_obs, vcap, fcap, buffers, nverts, nfaces))
+    return fail(PMVS_EINVAL, "invalid argument");
+  if (sc->lkept < 0) return fail(PMVS_EINVAL, "loop_mesh: no loop result on the device");
+  HIPCHK(hipSetDevice(sc->device));
+  return mesh_records(sc, sc->fpatches.p, sc->lkept, flags, first_target, num_targets, params, volume, min_obs, vcap, fcap,
+                      buffers, nverts, nfaces);
+}
+
+pmvs_status pmvs_mesh_patches(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, int32_t flags, int32_t first_target,
+                              int32_t num_targets, const pmvs_tsdf_params* params, const pmvs_volume* volume, int32_t min_obs,
+                              int64_t vcap, int64_t fcap, const pmvs_mesh_buffers* buffers, int64_t* nverts, int64_t* nfaces) {
+  if (!tsdf_args_ok(sc, flags, first_target, num_targets, params, volume) ||
+      !mesh_args_ok(min_obs, vcap, fcap, buffers, nverts, nfaces) || n < 0 || (n > 0 && !patches))
+    return fail(PMVS_EINVAL, "invalid argument");
+  if (pmvs_status st = check_export_patches(sc, patches, n, nullptr)) return st;
+  HIPCHK(hipSetDevice(sc->device));
+  ExportTemp tmp;
+  pmvs_patch* dP = nullptr;
+  if (pmvs_status st = upload_records(sc, patches, n, tmp, &dP)) return st;
+  return mesh_records(sc, dP, n, flags, first_target, num_targets, params, volume, min_obs, vcap, fcap, buffers, nverts, nfaces);
+}
+
 // ---- text files (pmvs_text.hip)
 namespace {
 bool text_args_ok(const pmvs_scene* sc, int32_t kind, int32_t flags, const char* out, int64_t cap, const int64_t* bytes) {

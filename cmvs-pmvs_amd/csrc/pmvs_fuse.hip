@@ -16,6 +16,8 @@
 //   fuse_gather_kernel    the emitted pixels below `cap` write the requested point arrays; the colour is
 //                         the pixel's RGBA8 pyramid word
 // Nothing depends on the order of the work, so the cloud is deterministic.
+// fuse_maps_pass is the first half (the maps and fuse_support_kernel) on its own: the TSDF integration
+// (pmvs_mesh.hip) starts from the same maps and pass flags.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -35,7 +37,7 @@ namespace {
     if (e_ != hipSuccess) return e_;      \
   } while (0)
 
-struct FuseMaps {        // the range's maps, by value to the kernels
+struct FuseMapsView {    // the range's maps, by value to the kernels
   const int* patch;
   const float *depth, *normal;
   const long long* off;  // count + 1: the first pixel of each target's map
@@ -44,7 +46,7 @@ struct FuseMaps {        // the range's maps, by value to the kernels
 
 // The pixel of the range's target j (wave-uniform) that the point S4 = (Sf, 1) with normal n is consistent
 // with, or -1.  Every index is guarded by pixel_at: q lies in target j's map.
-__device__ __forceinline__ long long consistent_pixel(const DScene& s, const FuseMaps& m, int j, const float* S4, const float* n,
+__device__ __forceinline__ long long consistent_pixel(const DScene& s, const FuseMapsView& m, int j, const float* S4, const float* n,
                                                       const pmvs_fuse_params& prm) {
   const DView& vs = s.views[m.first + j];
   const int W = vs.w[s.level], H = vs.h[s.level];
@@ -60,7 +62,7 @@ __device__ __forceinline__ long long consistent_pixel(const DScene& s, const Fus
 }
 
 // This thread's pixel: c = its index in the range's arrays, (u, v) in target j; false past the image.
-__device__ __forceinline__ bool own_pixel(const DScene& s, const FuseMaps& m, int* j, int* u, int* v, long long* c) {
+__device__ __forceinline__ bool own_pixel(const DScene& s, const FuseMapsView& m, int* j, int* u, int* v, long long* c) {
   *j = blockIdx.y;
   if (*j >= m.count) return false;
   const DView& vw = s.views[m.first + *j];
@@ -72,7 +74,7 @@ __device__ __forceinline__ bool own_pixel(const DScene& s, const FuseMaps& m, in
   return true;
 }
 
-__global__ __launch_bounds__(256) void fuse_support_kernel(DScene s, FuseMaps m, pmvs_fuse_params prm,
+__global__ __launch_bounds__(256) void fuse_support_kernel(DScene s, FuseMapsView m, pmvs_fuse_params prm,
                                                            unsigned char* __restrict__ support,
                                                            unsigned char* __restrict__ pass) {
   int j, u, v;
@@ -94,7 +96,7 @@ __global__ __launch_bounds__(256) void fuse_support_kernel(DScene s, FuseMaps m,
   pass[c] = cnt >= prm.min_support;
 }
 
-__global__ __launch_bounds__(256) void fuse_emit_kernel(DScene s, FuseMaps m, pmvs_fuse_params prm,
+__global__ __launch_bounds__(256) void fuse_emit_kernel(DScene s, FuseMapsView m, pmvs_fuse_params prm,
                                                         const unsigned char* __restrict__ pass, long long* __restrict__ pos) {
   int j, u, v;
   long long c;
@@ -117,7 +119,7 @@ __global__ __launch_bounds__(256) void fuse_emit_kernel(DScene s, FuseMaps m, pm
 }
 
 // pos: the inclusive sums of the emit flags.
-__global__ __launch_bounds__(256) void fuse_gather_kernel(DScene s, FuseMaps m, const unsigned char* __restrict__ support,
+__global__ __launch_bounds__(256) void fuse_gather_kernel(DScene s, FuseMapsView m, const unsigned char* __restrict__ support,
                                                           const long long* __restrict__ pos, long long cap, FuseArrays out) {
   int j, u, v;
   long long c;
@@ -148,9 +150,10 @@ __global__ __launch_bounds__(256) void fuse_gather_kernel(DScene s, FuseMaps m, 
 
 }  // namespace
 
-hipError_t fuse_pass(const DScene& s, const DView* hviews, const pmvs_patch* P, int n, const int* src, int first, int count,
-                     const pmvs_fuse_params& prm, long long cap, const FuseArrays& out, long long* total, hipStream_t st) {
-  std::vector<long long> off((size_t)count + 1);
+hipError_t fuse_maps_pass(const DScene& s, const DView* hviews, const pmvs_patch* P, int n, const int* src, int first, int count,
+                          const pmvs_fuse_params& prm, unsigned char* support_map, FuseMaps& f, hipStream_t st) {
+  std::vector<long long>& off = f.host_off;  // it outlives the asynchronous upload below
+  off.assign((size_t)count + 1, 0);
   long long pixels = 0, widest = 0;
   for (int j = 0; j < count; ++j) {
     const long long wh = (long long)hviews[first + j].w[s.level] * hviews[first + j].h[s.level];
@@ -161,38 +164,48 @@ hipError_t fuse_pass(const DScene& s, const DView* hviews, const pmvs_patch* P, 
   off[(size_t)count] = pixels;
   const long long rb = (widest + 255) / 256;
   if (rb > INT_MAX) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)(rb < 1 ? 1 : rb), (unsigned)count);
+  f.pixels = pixels;
+  f.row_blocks = (unsigned)(rb < 1 ? 1 : rb);
+  const dim3 grid(f.row_blocks, (unsigned)count);
 
-  DevBuf<int> patch;
-  DevBuf<float> depth, normal;
-  DevBuf<unsigned char> support, pass;
-  DevBuf<long long> d_off, pos;
-  DevBuf<char> temp;
-  FCHK(patch.alloc((size_t)pixels));
-  FCHK(depth.alloc((size_t)pixels));
-  FCHK(normal.alloc((size_t)pixels * 3));
-  FCHK(pass.alloc((size_t)pixels));
-  FCHK(pos.alloc((size_t)pixels));
-  FCHK(d_off.alloc(off.size()));
-  unsigned char* d_support = out.support_map;
-  if (!d_support) {
-    FCHK(support.alloc((size_t)pixels));
-    d_support = support.p;
+  FCHK(f.patch.alloc((size_t)pixels));
+  FCHK(f.depth.alloc((size_t)pixels));
+  FCHK(f.normal.alloc((size_t)pixels * 3));
+  FCHK(f.pass.alloc((size_t)pixels));
+  FCHK(f.off.alloc(off.size()));
+  f.support_map = support_map;
+  if (!f.support_map) {
+    FCHK(f.support.alloc((size_t)pixels));
+    f.support_map = f.support.p;
   }
+
+  // the maps, by the maps' own pass: the bytes pmvs_loop_pixel_maps gives in device mode
+  DepthMapArrays maps;
+  maps.patch = f.patch.p, maps.depth = f.depth.p, maps.normal = f.normal.p;
+  FCHK(pixel_map_pass(s, hviews, P, n, src, first, count, prm.radius, maps, st));
+
+  FCHK(hipMemcpyAsync(f.off.p, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+  const FuseMapsView m{f.patch.p, f.depth.p, f.normal.p, f.off.p, first, count};
+  hipLaunchKernelGGL(fuse_support_kernel, grid, dim3(256), 0, st, s, m, prm, f.support_map, f.pass.p);
+  return hipGetLastError();
+}
+
+hipError_t fuse_pass(const DScene& s, const DView* hviews, const pmvs_patch* P, int n, const int* src, int first, int count,
+                     const pmvs_fuse_params& prm, long long cap, const FuseArrays& out, long long* total, hipStream_t st) {
+  FuseMaps f;
+  DevBuf<long long> pos;
+  DevBuf<char> temp;
+  FCHK(fuse_maps_pass(s, hviews, P, n, src, first, count, prm, out.support_map, f, st));
+  const long long pixels = f.pixels;
+  const dim3 grid(f.row_blocks, (unsigned)count);
+  unsigned char* d_support = f.support_map;
+  const FuseMapsView m{f.patch.p, f.depth.p, f.normal.p, f.off.p, first, count};
+  FCHK(pos.alloc((size_t)pixels));
   size_t tb = 0;
   FCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, pos.p, pos.p, pixels, st));
   FCHK(temp.alloc(tb));
 
-  // the maps, by the maps' own pass: the bytes pmvs_loop_pixel_maps gives in device mode
-  DepthMapArrays maps;
-  maps.patch = patch.p, maps.depth = depth.p, maps.normal = normal.p;
-  FCHK(pixel_map_pass(s, hviews, P, n, src, first, count, prm.radius, maps, st));
-
-  FCHK(hipMemcpyAsync(d_off.p, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice, st));
-  const FuseMaps m{patch.p, depth.p, normal.p, d_off.p, first, count};
-  hipLaunchKernelGGL(fuse_support_kernel, grid, dim3(256), 0, st, s, m, prm, d_support, pass.p);
-  FCHK(hipGetLastError());
-  hipLaunchKernelGGL(fuse_emit_kernel, grid, dim3(256), 0, st, s, m, prm, pass.p, pos.p);
+  hipLaunchKernelGGL(fuse_emit_kernel, grid, dim3(256), 0, st, s, m, prm, f.pass.p, pos.p);
   FCHK(hipGetLastError());
   FCHK(hipcub::DeviceScan::InclusiveSum(temp.p, tb, pos.p, pos.p, pixels, st));
   long long cnt = 0;

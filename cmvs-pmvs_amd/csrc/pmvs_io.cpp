@@ -707,4 +707,78 @@ pmvs_status pmvs_write_ply_binary(const char* path, int64_t n, const float* coor
   return ofstr.good() ? PMVS_OK : pmvs_io_fail(PMVS_EINVAL, "write failed: %s", path);
 }
 
+// A mesh (pmvs_tsdf_mesh) as binary little-endian PLY: 27-byte vertex records, 13-byte face records.
+pmvs_status pmvs_write_ply_mesh_binary(const char* path, int64_t nv, const float* vertex, const float* normal,
+                                       const uint8_t* color, int64_t nf, const int32_t* face) {
+  if (!path || nv < 0 || nf < 0 || (nv > 0 && (!vertex || !normal || !color)) || (nf > 0 && !face))
+    return pmvs_io_fail(PMVS_EINVAL, "invalid argument");
+  std::ofstream ofstr(path, std::ios::binary);
+  if (!ofstr.is_open()) return pmvs_io_fail(PMVS_EINVAL, "cannot write %s", path);
+  ofstr << "ply\nformat binary_little_endian 1.0\nelement vertex " << nv
+        << "\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\n"
+           "property float nz\nproperty uchar diffuse_red\nproperty uchar diffuse_green\nproperty uchar diffuse_blue\n"
+           "element face "
+        << nf << "\nproperty list uchar int vertex_indices\nend_header\n";
+  constexpr int64_t kChunk = 4096;  // records per write
+  std::vector<char> buf((size_t)(kChunk * 27));
+  auto put32 = [](char* dst, uint32_t u) {
+    for (int j = 0; j < 4; ++j) dst[j] = (char)((u >> (8 * j)) & 0xff);
+  };
+  for (int64_t p0 = 0; p0 < nv; p0 += kChunk) {
+    const int64_t m = std::min<int64_t>(kChunk, nv - p0);
+    for (int64_t i = 0; i < m; ++i) {
+      char* rec = buf.data() + 27 * i;
+      const float f[6] = {vertex[3 * (p0 + i)], vertex[3 * (p0 + i) + 1], vertex[3 * (p0 + i) + 2],
+                          normal[3 * (p0 + i)], normal[3 * (p0 + i) + 1], normal[3 * (p0 + i) + 2]};
+      for (int k = 0; k < 6; ++k) {
+        uint32_t u;
+        std::memcpy(&u, f + k, 4);
+        put32(rec + 4 * k, u);
+      }
+      rec[24] = (char)color[3 * (p0 + i)], rec[25] = (char)color[3 * (p0 + i) + 1], rec[26] = (char)color[3 * (p0 + i) + 2];
+    }
+    ofstr.write(buf.data(), (std::streamsize)(27 * m));
+  }
+  for (int64_t p0 = 0; p0 < nf; p0 += kChunk) {
+    const int64_t m = std::min<int64_t>(kChunk, nf - p0);
+    for (int64_t i = 0; i < m; ++i) {
+      char* rec = buf.data() + 13 * i;
+      rec[0] = 3;
+      for (int k = 0; k < 3; ++k) put32(rec + 1 + 4 * k, (uint32_t)face[3 * (p0 + i) + k]);
+    }
+    ofstr.write(buf.data(), (std::streamsize)(13 * m));
+  }
+  return ofstr.good() ? PMVS_OK : pmvs_io_fail(PMVS_EINVAL, "write failed: %s", path);
+}
+
+// The volume `pmvs2 ... MESH` meshes a cloud in (include/pmvs_amd.h).
+pmvs_status pmvs_volume_from_points(int64_t n, const float* coord, int32_t cells, int32_t pad, pmvs_volume* volume) {
+  if (!coord || !volume || n < 1 || cells < 1 || pad < 0) return pmvs_io_fail(PMVS_EINVAL, "invalid argument");
+  float lo[3], hi[3];
+  for (int a = 0; a < 3; ++a) lo[a] = hi[a] = coord[a];
+  for (int64_t i = 0; i < n; ++i)
+    for (int a = 0; a < 3; ++a) {
+      const float c = coord[3 * i + a];
+      if (!std::isfinite(c)) return pmvs_io_fail(PMVS_EINVAL, "volume_from_points: point %lld is not finite", (long long)i);
+      lo[a] = std::min(lo[a], c);
+      hi[a] = std::max(hi[a], c);
+    }
+  double ext = 0.0;
+  for (int a = 0; a < 3; ++a) ext = std::max(ext, (double)hi[a] - (double)lo[a]);
+  pmvs_volume v{};
+  v.voxel = (float)(ext / (double)cells);
+  if (!std::isfinite(v.voxel) || !(v.voxel > 0.0f)) return pmvs_io_fail(PMVS_EINVAL, "volume_from_points: a box of no extent");
+  double voxels = 1.0;
+  for (int a = 0; a < 3; ++a) {
+    v.origin[a] = (float)((double)lo[a] - (double)pad * (double)v.voxel);
+    const double d = std::max(1.0, std::ceil(((double)hi[a] - (double)lo[a]) / (double)v.voxel)) + 2.0 * (double)pad;
+    if (!std::isfinite(v.origin[a]) || !(d <= 2147483647.0)) return pmvs_io_fail(PMVS_EINVAL, "volume_from_points: too large");
+    v.dims[a] = (int32_t)d;
+    voxels *= d;
+  }
+  if (voxels > 2147483647.0) return pmvs_io_fail(PMVS_EINVAL, "volume_from_points: more than 2^31-1 voxels");
+  *volume = v;
+  return PMVS_OK;
+}
+
 }  // extern "C"

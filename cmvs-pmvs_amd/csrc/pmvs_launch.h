@@ -180,6 +180,44 @@ struct FuseArrays {
 // maps' own) is freed by then.
 hipError_t fuse_pass(const DScene& s, const DView* hviews, const pmvs_patch* P, int n, const int* src, int first, int count,
                      const pmvs_fuse_params& prm, long long cap, const FuseArrays& out, long long* total, hipStream_t st);
+// Fuse steps 1-4 alone, for the consumers of the maps and the pass flags (fuse_pass itself, the TSDF
+// integration): the range's patch, depth and normal maps, the support map (into `support_map` when the
+// caller has one, else into `support`) and one pass flag per pixel, with the pixel offset of every target.
+// The work is enqueued on `st`, not waited for; `f` owns the arrays.
+struct FuseMaps {
+  DevBuf<int> patch;
+  DevBuf<float> depth, normal;
+  DevBuf<unsigned char> support, pass;
+  DevBuf<long long> off;            // count + 1
+  std::vector<long long> host_off;  // the same on the host
+  unsigned char* support_map = nullptr;
+  long long pixels = 0;
+  unsigned row_blocks = 1;          // blocks of 256 pixels that cover the largest image
+};
+hipError_t fuse_maps_pass(const DScene& s, const DView* hviews, const pmvs_patch* P, int n, const int* src, int first, int count,
+                          const pmvs_fuse_params& prm, unsigned char* support_map, FuseMaps& f, hipStream_t st);
+
+// ---- meshing of the fused maps (pmvs_mesh.hip; the definition is csrc/pmvs_mesh.h)
+// Device pointers of pmvs_tsdf_buffers / pmvs_mesh_buffers (include/pmvs_amd.h); null = not wanted.
+struct TsdfArrays {
+  float* tsdf = nullptr;
+  unsigned char *obs = nullptr, *color = nullptr;
+};
+struct MeshArrays {
+  float *vertex = nullptr, *normal = nullptr;
+  unsigned char* color = nullptr;
+  int* face = nullptr;
+};
+// The TSDF of `vol` integrated from the maps and pass flags `f` of targets [first, first + count), on `st`
+// (not waited for).
+hipError_t tsdf_integrate(const DScene& s, const FuseMaps& f, int first, int count, const pmvs_volume& vol, float trunc,
+                          const TsdfArrays& out, hipStream_t st);
+// Naive surface nets over the device volume arrays (color may be null): the first min(*nverts, vcap)
+// vertices and min(*nfaces, fcap) faces into `out`.  Returns after the stream has finished the work; its
+// scratch (5 bytes per cell, 9 per voxel) is freed by then.
+hipError_t tsdf_mesh_pass(const pmvs_volume& vol, int min_obs, const float* tsdf, const unsigned char* obs,
+                          const unsigned char* color, long long vcap, long long fcap, const MeshArrays& out, long long* nverts,
+                          long long* nfaces, hipStream_t st);
 
 // ---- filter pass (pmvs_filter.hip)
 // The fields of a patch that neighbour and visibility tests read from OTHER patches (isNeighbor,

@@ -129,6 +129,22 @@ class FuseBuffers(C.Structure):  # pmvs_fuse_buffers
     _fields_ = [(k, C.c_void_p) for k in ("support_map", "coord", "normal", "color", "support", "pixel", "patch")]
 
 
+class Volume(C.Structure):  # pmvs_volume
+    _fields_ = [("origin", C.c_float * 3), ("voxel", C.c_float), ("dims", C.c_int32 * 3)]
+
+
+class TsdfParams(C.Structure):  # pmvs_tsdf_params
+    _fields_ = [("fuse", FuseParams), ("trunc", C.c_float)]
+
+
+class TsdfBuffers(C.Structure):  # pmvs_tsdf_buffers
+    _fields_ = [(k, C.c_void_p) for k in ("tsdf", "obs", "color")]
+
+
+class MeshBuffers(C.Structure):  # pmvs_mesh_buffers
+    _fields_ = [(k, C.c_void_p) for k in ("vertex", "normal", "color", "face")]
+
+
 class SeedStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("trial", "pass_", "fail0", "fail1", "refined", "rounds", "candidates",
                                           "reserved")] + [(k, C.c_double) for k in ("wall_ms", "gen_ms", "refine_ms")]
@@ -175,6 +191,8 @@ EXPORTS = ["pmvs_last_error", "pmvs_device_count", "pmvs_scene_create", "pmvs_sc
            "pmvs_depth_map_layout", "pmvs_loop_depth_maps", "pmvs_depth_maps_patches", "pmvs_write_pfm",
            "pmvs_pixel_map_layout", "pmvs_loop_pixel_maps", "pmvs_pixel_maps_patches",
            "pmvs_loop_fuse", "pmvs_fuse_patches", "pmvs_write_ply_binary",
+           "pmvs_loop_tsdf", "pmvs_tsdf_patches", "pmvs_tsdf_mesh", "pmvs_loop_mesh", "pmvs_mesh_patches",
+           "pmvs_volume_from_points", "pmvs_write_ply_mesh_binary",
            "pmvs_loop_text", "pmvs_text_patches", "pmvs_selftest_format", "pmvs_selftest_labels",
            "pmvs_scene_set_shard", "pmvs_scene_set_shard_rccl", "pmvs_scene_set_cluster",
            "pmvs_scene_set_cluster_rccl", "pmvs_rccl_unique_id",
@@ -260,6 +278,16 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.pmvs_fuse_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(FuseParams),
                                       C.c_int64, C.POINTER(FuseBuffers), C.POINTER(C.c_int64)]
     lib.pmvs_write_ply_binary.argtypes = [C.c_char_p, C.c_int64] + [C.c_void_p] * 4
+    tsdf_tail = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(TsdfParams), C.POINTER(Volume)]  # flags, range, params, volume
+    mesh_tail = [C.c_int32, C.c_int64, C.c_int64, C.POINTER(MeshBuffers), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.pmvs_loop_tsdf.argtypes = [C.c_void_p] + tsdf_tail + [C.POINTER(TsdfBuffers)]
+    lib.pmvs_tsdf_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32] + tsdf_tail + [C.POINTER(TsdfBuffers)]
+    lib.pmvs_tsdf_mesh.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Volume), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_int64, C.c_int64, C.POINTER(MeshBuffers), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.pmvs_loop_mesh.argtypes = [C.c_void_p] + tsdf_tail + mesh_tail
+    lib.pmvs_mesh_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32] + tsdf_tail + mesh_tail
+    lib.pmvs_volume_from_points.argtypes = [C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Volume)]
+    lib.pmvs_write_ply_mesh_binary.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.pmvs_loop_text.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                    C.POINTER(C.c_int64)]
     lib.pmvs_text_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -789,6 +817,117 @@ class Scene:
         return self._fuse_call(lambda *a: self.lib.pmvs_fuse_patches(self.handle, _ptr(pa), len(pa), *a), writer_order,
                                device, arrays, first_target, num_targets, radius, min_support, depth_rel, normal_cos)
 
+    # pmvs_tsdf_buffers / pmvs_mesh_buffers: array name -> (dtype, trailing shape)
+    TSDF_ARRAYS = {"tsdf": ("float32", ()), "obs": ("uint8", ()), "color": ("uint8", (4,))}
+    MESH_ARRAYS = {"vertex": ("float32", "v"), "normal": ("float32", "v"), "color": ("uint8", "v"), "face": ("int32", "f")}
+
+    def _new_arrays(self, Buffers, spec, names, device):
+        """The arrays `names` of `spec` (name -> (dtype, shape)) as numpy arrays or torch tensors on the
+        scene's device, and the C struct that points at them (an empty array as NULL)."""
+        out, buf = {}, Buffers()
+        for k in names:
+            dt, shape = spec[k]
+            if device:
+                import torch
+                out[k] = torch.empty(shape, dtype=getattr(torch, dt), device=torch.device("cuda", self.device))
+                setattr(buf, k, out[k].data_ptr() if out[k].numel() else None)
+            else:
+                out[k] = np.empty(shape, dt)
+                setattr(buf, k, out[k].ctypes.data if out[k].size else None)
+        return out, buf
+
+    def _tsdf_params(self, volume, trunc, writer_order, device, first_target, num_targets, radius, min_support, depth_rel,
+                     normal_cos):
+        """(flags, first, num, byref(params), byref(volume)): the arguments the TSDF and mesh calls share."""
+        num = self.desc.num_targets - first_target if num_targets is None else num_targets
+        prm = TsdfParams(FuseParams(self.desc.csize if radius is None else radius, min_support, depth_rel, normal_cos), trunc)
+        flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
+        return flags, first_target, num, C.byref(prm), C.byref(volume)
+
+    def _tsdf_call(self, call, volume, device, arrays, shared):
+        nx, ny, nz = volume.dims
+        spec = {k: (dt, (nz, ny, nx) + tail) for k, (dt, tail) in self.TSDF_ARRAYS.items()}
+        out, buf = self._new_arrays(TsdfBuffers, spec, list(spec) if arrays is None else list(arrays), device)
+        _check(call(*shared, C.byref(buf)))
+        return out
+
+    def loop_tsdf(self, volume: Volume, trunc: float, writer_order: bool = True, device: bool = False, arrays=None,
+                  first_target: int = 0, num_targets=None, radius=None, min_support: int = 2, depth_rel: float = 0.01,
+                  normal_cos: float = 0.5) -> dict:
+        """pmvs_loop_tsdf: the TSDF of `volume` (P.volume(origin, voxel, dims)) integrated from the per-pixel
+        maps and the fusion's pass flags of the last run_loop(fetch=False) result over a target range,
+        keyed by the fields of pmvs_tsdf_buffers: tsdf [nz, ny, nx] float32 (positive outside, 1 where
+        unobserved), obs [nz, ny, nx] uint8 (the targets that observe the voxel), color [nz, ny, nx, 4]
+        uint8 (RGBA, A = 255 iff the voxel has a colour).  The other parameters are loop_fuse's.  Does
+        not consume the result.  device=True: torch tensors on the scene's device, written there."""
+        shared = self._tsdf_params(volume, trunc, writer_order, device, first_target, num_targets, radius, min_support,
+                                   depth_rel, normal_cos)
+        return self._tsdf_call(lambda *a: self.lib.pmvs_loop_tsdf(self.handle, *a), volume, device, arrays, shared)
+
+    def tsdf_patches(self, patches: np.ndarray, volume: Volume, trunc: float, writer_order: bool = True, device: bool = False,
+                     arrays=None, first_target: int = 0, num_targets=None, radius=None, min_support: int = 2,
+                     depth_rel: float = 0.01, normal_cos: float = 0.5) -> dict:
+        """pmvs_tsdf_patches: loop_tsdf's arrays for caller-supplied PATCH_DTYPE records."""
+        pa = np.ascontiguousarray(patches, PATCH_DTYPE)
+        shared = self._tsdf_params(volume, trunc, writer_order, device, first_target, num_targets, radius, min_support,
+                                   depth_rel, normal_cos)
+        return self._tsdf_call(lambda *a: self.lib.pmvs_tsdf_patches(self.handle, _ptr(pa), len(pa), *a), volume, device,
+                               arrays, shared)
+
+    def _mesh_call(self, call, device, arrays):
+        """call(vcap, fcap, byref(buffers), byref(nverts), byref(nfaces)): a counting call, then the arrays."""
+        nv, nf = C.c_int64(0), C.c_int64(0)
+        _check(call(0, 0, C.byref(MeshBuffers()), C.byref(nv), C.byref(nf)))
+        v, f = int(nv.value), int(nf.value)
+        spec = {k: (dt, (v if n == "v" else f, 3)) for k, (dt, n) in self.MESH_ARRAYS.items()}
+        out, buf = self._new_arrays(MeshBuffers, spec, list(spec) if arrays is None else list(arrays), device)
+        _check(call(v, f, C.byref(buf), C.byref(nv), C.byref(nf)))
+        if (int(nv.value), int(nf.value)) != (v, f):
+            raise PmvsError(f"the mesh has {nv.value} vertices and {nf.value} faces after counting {v} and {f}")
+        return out
+
+    def tsdf_mesh(self, volume: Volume, tsdf, obs, color=None, min_obs: int = 1, device: bool = False, arrays=None) -> dict:
+        """pmvs_tsdf_mesh: the naive-surface-nets mesh of a volume (tsdf and obs [nz, ny, nx], color
+        [nz, ny, nx, 4] or None), keyed by the fields of pmvs_mesh_buffers: vertex [nv, 3] and normal
+        [nv, 3] float32, color [nv, 3] uint8, face [nf, 3] int32 (vertex ids, outward facing).  A voxel
+        counts as observed from min_obs observations on.  The arrays are sized by a counting call first.
+        device=True: the volume arrays are torch tensors on the scene's device and so is the mesh."""
+        voxels = volume.dims[0] * volume.dims[1] * volume.dims[2]
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            ins = [torch.as_tensor(a, dtype=dt, device=dev).contiguous() if a is not None else None
+                   for a, dt in ((tsdf, torch.float32), (obs, torch.uint8), (color, torch.uint8))]
+            sizes, ptrs = [0 if a is None else a.numel() for a in ins], [None if a is None else a.data_ptr() for a in ins]
+        else:
+            ins = [np.ascontiguousarray(a, dt) if a is not None else None
+                   for a, dt in ((tsdf, np.float32), (obs, np.uint8), (color, np.uint8))]
+            sizes, ptrs = [0 if a is None else a.size for a in ins], [_ptr(a) for a in ins]
+        if sizes[:2] != [voxels, voxels] or sizes[2] not in (0, 4 * voxels):
+            raise ValueError("tsdf_mesh: the arrays do not have the volume's size")
+        flags = EXPORT_DEVICE if device else 0
+        return self._mesh_call(lambda *a: self.lib.pmvs_tsdf_mesh(self.handle, flags, C.byref(volume), min_obs, *ptrs, *a),
+                               device, arrays)
+
+    def loop_mesh(self, volume: Volume, trunc: float, min_obs: int = 1, writer_order: bool = True, device: bool = False,
+                  arrays=None, first_target: int = 0, num_targets=None, radius=None, min_support: int = 2,
+                  depth_rel: float = 0.01, normal_cos: float = 0.5) -> dict:
+        """pmvs_loop_mesh: loop_tsdf then tsdf_mesh in one call, the volume never leaving the device;
+        tsdf_mesh's arrays.  The counting call integrates too, so the integration runs twice."""
+        shared = self._tsdf_params(volume, trunc, writer_order, device, first_target, num_targets, radius, min_support,
+                                   depth_rel, normal_cos)
+        return self._mesh_call(lambda *a: self.lib.pmvs_loop_mesh(self.handle, *shared, min_obs, *a), device, arrays)
+
+    def mesh_patches(self, patches: np.ndarray, volume: Volume, trunc: float, min_obs: int = 1, writer_order: bool = True,
+                     device: bool = False, arrays=None, first_target: int = 0, num_targets=None, radius=None,
+                     min_support: int = 2, depth_rel: float = 0.01, normal_cos: float = 0.5) -> dict:
+        """pmvs_mesh_patches: loop_mesh's arrays for caller-supplied PATCH_DTYPE records."""
+        pa = np.ascontiguousarray(patches, PATCH_DTYPE)
+        shared = self._tsdf_params(volume, trunc, writer_order, device, first_target, num_targets, radius, min_support,
+                                   depth_rel, normal_cos)
+        return self._mesh_call(lambda *a: self.lib.pmvs_mesh_patches(self.handle, _ptr(pa), len(pa), *shared, min_obs, *a),
+                               device, arrays)
+
     def _text(self, call, device: bool, out):
         """A size query, the buffer (numpy uint8, or a torch uint8 tensor on the scene's device; `out`
         supplies it) and the call that fills it; returns the buffer cut to the text's size."""
@@ -1011,6 +1150,33 @@ def write_ply_binary(path: str, coord, normal, color, support):
     if not len(c) == len(nm) == len(col) == len(sup):
         raise ValueError("write_ply_binary takes arrays of one length")
     _check(load_library().pmvs_write_ply_binary(path.encode(), len(c), _ptr(c), _ptr(nm), _ptr(col), _ptr(sup)))
+
+
+def volume(origin, voxel: float, dims) -> Volume:
+    """A pmvs_volume: nx x ny x nz = dims voxels of edge `voxel` from the corner `origin`; voxel (i, j, k)
+    has index (k * ny + j) * nx + i."""
+    return Volume((C.c_float * 3)(*[float(x) for x in origin]), float(voxel), (C.c_int32 * 3)(*[int(x) for x in dims]))
+
+
+def volume_from_points(coord, cells: int = 256, pad: int = 3) -> Volume:
+    """pmvs_volume_from_points: the volume `pmvs2 ... MESH` meshes a cloud in: its bounding box padded by
+    `pad` voxels on every side, the voxel the box's longest extent / cells."""
+    c = np.ascontiguousarray(coord, np.float32).reshape(-1, 3)
+    v = Volume()
+    _check(load_library().pmvs_volume_from_points(len(c), _ptr(c), cells, pad, C.byref(v)))
+    return v
+
+
+def write_ply_mesh_binary(path: str, vertex, normal, color, face):
+    """pmvs_write_ply_mesh_binary: a mesh (Scene.tsdf_mesh's vertex, normal, color, face) as one binary
+    little-endian PLY of 27-byte vertices and 13-byte faces."""
+    v = np.ascontiguousarray(vertex, np.float32).reshape(-1, 3)
+    nm = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+    col = np.ascontiguousarray(color, np.uint8).reshape(-1, 3)
+    f = np.ascontiguousarray(face, np.int32).reshape(-1, 3)
+    if not len(v) == len(nm) == len(col):
+        raise ValueError("write_ply_mesh_binary takes vertex arrays of one length")
+    _check(load_library().pmvs_write_ply_mesh_binary(path.encode(), len(v), _ptr(v), _ptr(nm), _ptr(col), len(f), _ptr(f)))
 
 
 def write_pfm(path: str, data):

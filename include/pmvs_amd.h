@@ -530,6 +530,130 @@ pmvs_status pmvs_fuse_patches(pmvs_scene* scene, const pmvs_patch* patches, int3
 pmvs_status pmvs_write_ply_binary(const char* path, int64_t n, const float* coord, const float* normal,
                                   const uint8_t* color, const uint8_t* support);
 
+/* The fused maps meshed on the device, in two stages: a truncated signed distance (TSDF) volume integrated
+ * from the per-pixel maps and the fusion's pass flags, and a triangle mesh extracted from a volume by naive
+ * surface nets (no case table; a closed manifold wherever the volume is closed).  There is no reference
+ * for this; the definition below is the contract (csrc/pmvs_mesh.h implements it once, for host and
+ * device).  All f64 arithmetic is unfused, sums left to right in the stated order, as for the maps.
+ *
+ * The volume is an axis-aligned box of nx x ny x nz voxels of edge `voxel` from `origin`; voxel (i, j, k)
+ * has index ((k*ny)+j)*nx + i (x fastest).
+ *
+ * INTEGRATION (pmvs_loop_tsdf, pmvs_tsdf_patches).  The inputs are the range's patch, depth and normal maps
+ * and the fusion's pass(p) flags (pmvs_loop_fuse step 4) for params->fuse: the code pmvs_loop_fuse runs
+ * computes them, so they are the same bytes.  For voxel (i, j, k):
+ *  1. Cf[a] = (float)((double)origin[a] + ((double)idx_a + 0.5) * (double)voxel).
+ *  2. For each target t of the range, ascending: (x, y) = CCamera::project(view t, (Cf, 1.0f), level) and
+ *     z = OpticalAxis(t) * (Cf, 1.0f) in f32; px = floor((double)x + 0.5), py likewise, the inside test in
+ *     double (fuse step 3).  t observes the voxel iff q = (t, px, py) is inside the image, pass(q), z > 0,
+ *     and with d the depth at q, s = (double)d - (double)z >= -(double)trunc.  Then
+ *     v = s >= (double)trunc ? 1.0 : s / (double)trunc, sum += v, n += 1; and if s < (double)trunc the
+ *     three bytes of pixel q of target t's level image are added to three integer sums and nc += 1.
+ *  3. tsdf = n ? (float)(sum / (double)n) : 1.0f; obs = min(n, 255);
+ *     color = nc ? ((sum_c + nc/2) / nc per channel, 255) : (0, 0, 0, 0), integer division.
+ * The TSDF is positive outside the surface.  Nothing depends on the order of the work.
+ *
+ * EXTRACTION (pmvs_tsdf_mesh).  observed = obs >= min_obs, inside = tsdf < 0.
+ *  Cells: cell (i, j, k), 0 <= i < nx-1 and likewise j, k, has index ((k*(ny-1))+j)*(nx-1) + i; its corner c
+ *   is the voxel (i + (c&1), j + ((c>>1)&1), k + (c>>2)).  A cell is active iff all 8 corners are observed
+ *   and their inside flags are not all equal.
+ *  Edges: a cell's 12 edges in order: the four x-edges with (y, z) offsets 00, 10, 01, 11, the four y-edges
+ *   with (z, x) offsets in that pattern, the four z-edges with (x, y) offsets; each from the lower corner
+ *   (value v0) to the upper (v1).  An edge crosses when its two inside flags differ; then
+ *   t = (double)v0 / ((double)v0 - (double)v1) and its crossing point in cell units is the lower corner's
+ *   offset plus t along the edge's axis.
+ *  Vertex of an active cell: m = the sum of the crossing points (per component, in edge order) divided by
+ *   their count; vertex[a] = (float)((double)origin[a] + ((double)idx_a + 0.5 + m_a) * (double)voxel).
+ *  Normal: g_a = the sum of ((double)v1 - (double)v0) over axis a's four edges in edge order,
+ *   len = sqrt(gx*gx + gy*gy + gz*gz), normal[a] = (float)(g_a / len); zero when len is 0 or not finite.
+ *   It points outward.
+ *  Colour: per channel (sum + m/2) / m over the m corners whose A byte is 255, integer division; 0 when
+ *   m = 0 or color is NULL.
+ *  Vertices are emitted in ascending cell index.
+ *  Faces: for every voxel (i, j, k) in ascending index and every axis a in x, y, z order, with (a, b, c) the
+ *   cyclic permutation of (x, y, z) that starts at a: the edge to the +a neighbour is considered iff that
+ *   neighbour exists, 1 <= idx_b <= n_b-2 and 1 <= idx_c <= n_c-2; it emits iff both endpoints are
+ *   observed, their inside flags differ, and the four cells with a-coordinate idx_a and (b, c) coordinates
+ *   Q0 = (idx_b-1, idx_c-1), Q1 = (idx_b, idx_c-1), Q2 = (idx_b, idx_c), Q3 = (idx_b-1, idx_c) are all
+ *   active.  If the lower endpoint is inside it emits the two consecutive triangles (Q0, Q1, Q2),
+ *   (Q0, Q2, Q3) as vertex ids, otherwise (Q0, Q2, Q1), (Q0, Q3, Q2): either way they face outward.
+ *  *nverts and *nfaces receive the full counts; only the first min(count, cap) entries are written and
+ *  nothing past a cap; caps 0 with NULL arrays is the counting call.  A volume with a dim of 1 has no cells
+ *  and gives an empty mesh.
+ *
+ * flags, the target range, record validation, the use of the loop's result and device / host mode are
+ * those of the fuse calls; with PMVS_EXPORT_DEVICE every array pointer is a device pointer on the scene's
+ * device.  pmvs_tsdf_mesh takes only the device and stream from the scene, and of the flags only
+ * PMVS_EXPORT_DEVICE.  pmvs_loop_mesh / pmvs_mesh_patches integrate and extract in one call; the volume
+ * never leaves the device.
+ * PMVS_EINVAL: a NULL scene, volume, params, buffers or count pointer (pmvs_tsdf_mesh: a NULL tsdf or obs);
+ * another flag bit; the fuse calls' range and parameter checks; a non-finite origin; voxel or trunc not
+ * finite or <= 0; a dim < 1 or nx*ny*nz > 2^31-1; min_obs outside 1..255; a negative cap; no loop result.
+ * PMVS_ENOMEM when the device cannot hold the scratch.  Integration: 22 bytes per pixel of the RANGE (patch
+ * 4, depth 4, normal 12, support 1, pass 1) and the pixel maps' own scratch; nothing per voxel but the
+ * outputs (in host mode the requested ones staged on the device, at most 9 bytes per voxel; the combined
+ * calls always hold all 9).  Extraction: 5 bytes per cell (active flag 1, vertex id 4), 9 bytes per voxel
+ * (face flags 1, face offset 8) and the scan's temporary storage; in host mode also the volume (9 bytes
+ * per voxel) and the requested mesh arrays for min(cap, cells) vertices and min(cap, 6 * voxels) faces.
+ * All of it is allocated for the call and freed on return; the calls return after their work has finished. */
+typedef struct pmvs_volume {
+  float   origin[3];  /* finite: the corner of voxel (0, 0, 0) */
+  float   voxel;      /* finite, > 0: the voxels' edge */
+  int32_t dims[3];    /* nx, ny, nz >= 1, nx*ny*nz <= 2^31-1 */
+} pmvs_volume;
+
+typedef struct pmvs_tsdf_params {
+  pmvs_fuse_params fuse;  /* the maps and pass flags integrated */
+  float            trunc; /* finite, > 0: the truncation distance, in the scene's units */
+} pmvs_tsdf_params;
+
+typedef struct pmvs_tsdf_buffers {  /* any pointer may be NULL: that array is skipped */
+  float*   tsdf;   /* voxels */
+  uint8_t* obs;    /* voxels */
+  uint8_t* color;  /* voxels x 4: RGBA, A = 255 iff the voxel has a colour; a device pointer is 4-byte aligned */
+} pmvs_tsdf_buffers;
+
+typedef struct pmvs_mesh_buffers {  /* any pointer may be NULL: that array is skipped */
+  float*   vertex;  /* vcap x 3 */
+  float*   normal;  /* vcap x 3 */
+  uint8_t* color;   /* vcap x 3 */
+  int32_t* face;    /* fcap x 3: vertex ids */
+} pmvs_mesh_buffers;
+
+/* Reads the result pmvs_run_loop left on the device and does not consume it. */
+pmvs_status pmvs_loop_tsdf(pmvs_scene* scene, int32_t flags, int32_t first_target, int32_t num_targets,
+                           const pmvs_tsdf_params* params, const pmvs_volume* volume, const pmvs_tsdf_buffers* buffers);
+/* The same for caller-supplied records, validated and uploaded as pmvs_fuse_patches does. */
+pmvs_status pmvs_tsdf_patches(pmvs_scene* scene, const pmvs_patch* patches, int32_t n, int32_t flags,
+                              int32_t first_target, int32_t num_targets, const pmvs_tsdf_params* params,
+                              const pmvs_volume* volume, const pmvs_tsdf_buffers* buffers);
+/* The mesh of caller-supplied volume arrays (tsdf and obs one value per voxel, color 4 bytes per voxel or
+ * NULL; a device color pointer is 4-byte aligned). */
+pmvs_status pmvs_tsdf_mesh(pmvs_scene* scene, int32_t flags, const pmvs_volume* volume, int32_t min_obs,
+                           const float* tsdf, const uint8_t* obs, const uint8_t* color, int64_t vcap, int64_t fcap,
+                           const pmvs_mesh_buffers* buffers, int64_t* nverts, int64_t* nfaces);
+/* Integration then extraction. */
+pmvs_status pmvs_loop_mesh(pmvs_scene* scene, int32_t flags, int32_t first_target, int32_t num_targets,
+                           const pmvs_tsdf_params* params, const pmvs_volume* volume, int32_t min_obs, int64_t vcap,
+                           int64_t fcap, const pmvs_mesh_buffers* buffers, int64_t* nverts, int64_t* nfaces);
+pmvs_status pmvs_mesh_patches(pmvs_scene* scene, const pmvs_patch* patches, int32_t n, int32_t flags,
+                              int32_t first_target, int32_t num_targets, const pmvs_tsdf_params* params,
+                              const pmvs_volume* volume, int32_t min_obs, int64_t vcap, int64_t fcap,
+                              const pmvs_mesh_buffers* buffers, int64_t* nverts, int64_t* nfaces);
+/* The volume `pmvs2 ... MESH` uses for a point cloud (host coord, n x 3): with lo, hi the cloud's bounding
+ * box, voxel = (float)(max_a((double)hi[a] - (double)lo[a]) / (double)cells), origin[a] =
+ * (float)((double)lo[a] - (double)pad * (double)voxel) and dims[a] = max(1, ceil(((double)hi[a] -
+ * (double)lo[a]) / (double)voxel)) + 2 * pad.  PMVS_EINVAL for a NULL pointer, n < 1, cells < 1, pad < 0, a
+ * point that is not finite, a box of no extent, or a volume past the limits above. */
+pmvs_status pmvs_volume_from_points(int64_t n, const float* coord, int32_t cells, int32_t pad, pmvs_volume* volume);
+/* A mesh as one binary PLY: the header `format binary_little_endian 1.0`, `element vertex nv`, float x y z
+ * nx ny nz, uchar diffuse_red diffuse_green diffuse_blue, `element face nf`, `property list uchar int
+ * vertex_indices`; then nv 27-byte vertex records and nf 13-byte face records (the count 3 and three ids).
+ * Host arrays.  PMVS_EINVAL for a NULL path, a negative count, a NULL array with a positive count, or a
+ * file that cannot be written. */
+pmvs_status pmvs_write_ply_mesh_binary(const char* path, int64_t nv, const float* vertex, const float* normal,
+                                       const uint8_t* color, int64_t nf, const int32_t* face);
+
 /* The .ply / .patch / .pset text of the model, formatted on the device: the bytes pmvs_write_ply /
  * pmvs_write_patches / pmvs_write_pset write from the export of the same records and flags
  * (CPatchOrganizerS::writePLY patchOrganizerS.cpp:687-776, writePatches2 :89-132 with Patch::operator<<
