@@ -1395,22 +1395,9 @@ pmvs_status pmvs_loop_hash(pmvs_scene* sc, uint64_t* hash) {
   return PMVS_OK;
 }
 
-// ---- model export (pmvs_export.hip)
+// ---- the model-output calls: what every stage below shares
 namespace {
-struct ExportTemp {  // device memory of one export call, freed when the call returns
-  std::vector<void*> ptrs;
-  template <class T>
-  hipError_t alloc(T** p, size_t count) {
-    void* v = nullptr;
-    const hipError_t e = hipMalloc(&v, std::max(count, (size_t)1) * sizeof(T));
-    if (e == hipSuccess) ptrs.push_back(v);
-    *p = static_cast<T*>(v);
-    return e;
-  }
-  ~ExportTemp() {
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-};
+static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "output array types");
 
 pmvs_status export_status(hipError_t e, const char* what) {
   if (e == hipErrorOutOfMemory) return fail(PMVS_ENOMEM, "%s: %s", what, hipGetErrorString(e));
@@ -1421,6 +1408,25 @@ pmvs_status export_status(hipError_t e, const char* what) {
     const hipError_t e_ = (expr);                            \
     if (e_ != hipSuccess) return export_status(e_, #expr);   \
   } while (0)
+
+bool flags_ok(int32_t flags, int32_t allowed = PMVS_EXPORT_WRITER_ORDER | PMVS_EXPORT_DEVICE) { return !(flags & ~allowed); }
+bool records_ok(const pmvs_patch* patches, int32_t n) { return n >= 0 && (n == 0 || patches); }
+
+// Target t's cell grid and the maps' cell offsets (tnum + 1 entries); returns the widest grid.
+int depth_map_layout(const pmvs_scene* sc, int32_t* dims, int64_t* offsets) {
+  int64_t off = 0;
+  int max_gwidth = 1;
+  for (int t = 0; t < sc->ds.tnum; ++t) {
+    const int gw = (sc->hviews[t].w[sc->ds.level] + sc->ds.csize - 1) / sc->ds.csize;
+    const int gh = (sc->hviews[t].h[sc->ds.level] + sc->ds.csize - 1) / sc->ds.csize;
+    if (dims) { dims[2 * t] = gw; dims[2 * t + 1] = gh; }
+    if (offsets) offsets[t] = off;
+    off += (int64_t)gw * gh;
+    max_gwidth = std::max(max_gwidth, gw);
+  }
+  if (offsets) offsets[sc->ds.tnum] = off;
+  return max_gwidth;
+}
 
 pmvs_status check_export_patches(const pmvs_scene* sc, const pmvs_patch* patches, int32_t n, pmvs_export_sizes* sizes) {
   long long ni = 0, nv = 0;
@@ -1439,11 +1445,60 @@ pmvs_status check_export_patches(const pmvs_scene* sc, const pmvs_patch* patches
   return PMVS_OK;
 }
 
+// The records of a loop_* call: the loop result where it lies (`call` names the entry point in the message).
+pmvs_status loop_records(pmvs_scene* sc, const char* call, const pmvs_patch** dP, int32_t* n) {
+  if (sc->lkept < 0) return fail(PMVS_EINVAL, "%s: no loop result on the device", call);
+  HIPCHK(hipSetDevice(sc->device));
+  *dP = sc->fpatches.p;
+  *n = sc->lkept;
+  return PMVS_OK;
+}
+
+// The records of a *_patches call: validated (sizes = their totals, or null) and uploaded into a buffer of
+// the call's own (sc->fpatches may hold a loop result).
+pmvs_status upload_records(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, pmvs_export_sizes* sizes, CallArena& arena,
+                           const pmvs_patch** dP) {
+  *dP = nullptr;
+  if (pmvs_status st = check_export_patches(sc, patches, n, sizes)) return st;
+  HIPCHK(hipSetDevice(sc->device));
+  if (n) {
+    pmvs_patch* up = nullptr;
+    EXPCHK(arena.alloc(&up, (size_t)n));
+    EXPCHK(hipMemcpyAsync(up, patches, (size_t)n * sizeof(pmvs_patch), hipMemcpyHostToDevice, sc->stream));
+    *dP = up;
+  }
+  return PMVS_OK;
+}
+
+// Row r of a writer-ordered call is record d_src[r]: the export's order, from the export's code.  Null in
+// model order and without records.
+pmvs_status writer_order_source(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, int32_t flags, CallArena& arena, int** d_src) {
+  *d_src = nullptr;
+  if ((flags & PMVS_EXPORT_WRITER_ORDER) && n > 0) {
+    EXPCHK(arena.alloc(d_src, (size_t)n));
+    EXPCHK(export_order(sc->ds, dP, n, depth_map_layout(sc, nullptr, nullptr), *d_src, nullptr, nullptr, sc->stream));
+  }
+  return PMVS_OK;
+}
+
+// index2image on the device, or null (identity).
+pmvs_status upload_index2image(pmvs_scene* sc, const int32_t* index2image, CallArena& arena, int** d_tab) {
+  *d_tab = nullptr;
+  if (index2image) {
+    EXPCHK(arena.alloc(d_tab, (size_t)sc->ds.num));
+    EXPCHK(hipMemcpyAsync(*d_tab, index2image, (size_t)sc->ds.num * sizeof(int), hipMemcpyHostToDevice, sc->stream));
+  }
+  return PMVS_OK;
+}
+}  // namespace
+
+// ---- model export (pmvs_export.hip)
+namespace {
 pmvs_status device_export_sizes(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, pmvs_export_sizes* sizes) {
-  ExportTemp tmp;
+  CallArena arena;
   unsigned long long* d_tot = nullptr;
   unsigned long long tot[2] = {0, 0};
-  EXPCHK(tmp.alloc(&d_tot, 2));
+  EXPCHK(arena.alloc(&d_tot, 2));
   EXPCHK(export_sizes(dP, n, d_tot, sc->stream));
   EXPCHK(hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, sc->stream));
   EXPCHK(hipStreamSynchronize(sc->stream));
@@ -1464,143 +1519,90 @@ pmvs_status export_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, cons
     if (dev) EXPCHK(hipStreamSynchronize(sc->stream));
     return PMVS_OK;
   }
-  ExportTemp tmp;
+  CallArena arena;
+  Staging stg(arena, dev);
   int* d_tab = nullptr;
-  if (index2image) {
-    EXPCHK(tmp.alloc(&d_tab, (size_t)sc->ds.num));
-    EXPCHK(hipMemcpyAsync(d_tab, index2image, (size_t)sc->ds.num * sizeof(int), hipMemcpyHostToDevice, sc->stream));
-  }
-  int max_gwidth = 1;
-  for (int t = 0; t < sc->ds.tnum; ++t)
-    max_gwidth = std::max(max_gwidth, (sc->hviews[t].w[sc->ds.level] + sc->ds.csize - 1) / sc->ds.csize);
-  static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "export array types");
+  if (pmvs_status st = upload_index2image(sc, index2image, arena, &d_tab)) return st;
   const size_t np = (size_t)n, ne = (size_t)sz.image_entries, nve = (size_t)sz.vimage_entries;
   ExportArrays a;
-  if (dev) {  // straight into the caller's device buffers
-    a.fields = b->fields; a.colors = b->colors; a.image_off = (long long*)b->image_off; a.image_ids = b->image_ids;
-    a.image_idx = b->image_idx; a.vimage_off = (long long*)b->vimage_off; a.vimage_ids = b->vimage_ids; a.source = b->source;
-  } else {    // device staging for the requested arrays
-    if (b->fields) EXPCHK(tmp.alloc(&a.fields, np * 11));
-    if (b->colors) EXPCHK(tmp.alloc(&a.colors, np * 3));
-    if (b->image_off) EXPCHK(tmp.alloc(&a.image_off, np + 1));
-    if (b->image_ids) EXPCHK(tmp.alloc(&a.image_ids, ne));
-    if (b->image_idx) EXPCHK(tmp.alloc(&a.image_idx, ne));
-    if (b->vimage_off) EXPCHK(tmp.alloc(&a.vimage_off, np + 1));
-    if (b->vimage_ids) EXPCHK(tmp.alloc(&a.vimage_ids, nve));
-    if (b->source) EXPCHK(tmp.alloc(&a.source, np));
-  }
-  EXPCHK(export_pass(sc->ds, dP, n, (flags & PMVS_EXPORT_WRITER_ORDER) != 0, max_gwidth, d_tab, a, sc->stream));
-  if (!dev) {
-    auto down = [&](void* dst, const void* src, size_t bytes) {
-      return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sc->stream) : hipSuccess;
-    };
-    EXPCHK(down(b->fields, a.fields, np * 11 * sizeof(float)));
-    EXPCHK(down(b->colors, a.colors, np * 3 * sizeof(int32_t)));
-    EXPCHK(down(b->image_off, a.image_off, (np + 1) * sizeof(int64_t)));
-    EXPCHK(down(b->image_ids, a.image_ids, ne * sizeof(int32_t)));
-    EXPCHK(down(b->image_idx, a.image_idx, ne * sizeof(int32_t)));
-    EXPCHK(down(b->vimage_off, a.vimage_off, (np + 1) * sizeof(int64_t)));
-    EXPCHK(down(b->vimage_ids, a.vimage_ids, nve * sizeof(int32_t)));
-    EXPCHK(down(b->source, a.source, np * sizeof(int32_t)));
-    EXPCHK(hipStreamSynchronize(sc->stream));
-  }
+  EXPCHK(stg.fixed(&a.fields, b->fields, np * 11));
+  EXPCHK(stg.fixed(&a.colors, b->colors, np * 3));
+  EXPCHK(stg.fixed(&a.image_off, b->image_off, np + 1));
+  EXPCHK(stg.fixed(&a.image_ids, b->image_ids, ne));
+  EXPCHK(stg.fixed(&a.image_idx, b->image_idx, ne));
+  EXPCHK(stg.fixed(&a.vimage_off, b->vimage_off, np + 1));
+  EXPCHK(stg.fixed(&a.vimage_ids, b->vimage_ids, nve));
+  EXPCHK(stg.fixed(&a.source, b->source, np));
+  EXPCHK(export_pass(sc->ds, dP, n, (flags & PMVS_EXPORT_WRITER_ORDER) != 0, depth_map_layout(sc, nullptr, nullptr), d_tab, a,
+                     sc->stream));
+  EXPCHK(stg.finish(sc->stream));
   return PMVS_OK;
 }
 }  // namespace
 
 pmvs_status pmvs_loop_export_sizes(pmvs_scene* sc, pmvs_export_sizes* sizes) {
   if (!sc || !sizes) return fail(PMVS_EINVAL, "invalid argument");
-  if (sc->lkept < 0) return fail(PMVS_EINVAL, "loop_export_sizes: no loop result on the device");
-  HIPCHK(hipSetDevice(sc->device));
-  return device_export_sizes(sc, sc->fpatches.p, sc->lkept, sizes);
+  const pmvs_patch* dP = nullptr;
+  int32_t n = 0;
+  if (pmvs_status st = loop_records(sc, "loop_export_sizes", &dP, &n)) return st;
+  return device_export_sizes(sc, dP, n, sizes);
 }
 
 pmvs_status pmvs_loop_export(pmvs_scene* sc, int32_t flags, const int32_t* index2image, const pmvs_export_buffers* buffers) {
-  if (!sc || !buffers || (flags & ~(PMVS_EXPORT_WRITER_ORDER | PMVS_EXPORT_DEVICE))) return fail(PMVS_EINVAL, "invalid argument");
-  if (sc->lkept < 0) return fail(PMVS_EINVAL, "loop_export: no loop result on the device");
-  HIPCHK(hipSetDevice(sc->device));
+  if (!sc || !buffers || !flags_ok(flags)) return fail(PMVS_EINVAL, "invalid argument");
+  const pmvs_patch* dP = nullptr;
+  int32_t n = 0;
+  if (pmvs_status st = loop_records(sc, "loop_export", &dP, &n)) return st;
   pmvs_export_sizes sz{};
-  if (pmvs_status st = device_export_sizes(sc, sc->fpatches.p, sc->lkept, &sz)) return st;
-  return export_records(sc, sc->fpatches.p, sc->lkept, sz, flags, index2image, buffers);
+  if (pmvs_status st = device_export_sizes(sc, dP, n, &sz)) return st;
+  return export_records(sc, dP, n, sz, flags, index2image, buffers);
 }
 
 pmvs_status pmvs_export_patches_sizes(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, pmvs_export_sizes* sizes) {
-  if (!sc || !sizes || n < 0 || (n > 0 && !patches)) return fail(PMVS_EINVAL, "invalid argument");
+  if (!sc || !sizes || !records_ok(patches, n)) return fail(PMVS_EINVAL, "invalid argument");
   return check_export_patches(sc, patches, n, sizes);
 }
 
 pmvs_status pmvs_export_patches(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, int32_t flags,
                                 const int32_t* index2image, const pmvs_export_buffers* buffers) {
-  if (!sc || !buffers || n < 0 || (n > 0 && !patches) || (flags & ~(PMVS_EXPORT_WRITER_ORDER | PMVS_EXPORT_DEVICE)))
-    return fail(PMVS_EINVAL, "invalid argument");
+  if (!sc || !buffers || !records_ok(patches, n) || !flags_ok(flags)) return fail(PMVS_EINVAL, "invalid argument");
+  CallArena arena;
+  const pmvs_patch* dP = nullptr;
   pmvs_export_sizes sz{};
-  if (pmvs_status st = check_export_patches(sc, patches, n, &sz)) return st;
-  HIPCHK(hipSetDevice(sc->device));
-  // a buffer of its own: sc->fpatches may hold a loop result
-  ExportTemp tmp;
-  pmvs_patch* dP = nullptr;
-  if (n) {
-    EXPCHK(tmp.alloc(&dP, (size_t)n));
-    EXPCHK(hipMemcpyAsync(dP, patches, (size_t)n * sizeof(pmvs_patch), hipMemcpyHostToDevice, sc->stream));
-  }
+  if (pmvs_status st = upload_records(sc, patches, n, &sz, arena, &dP)) return st;
   return export_records(sc, dP, n, sz, flags, index2image, buffers);
 }
 
 // ---- per-target depth maps (pmvs_depthmap.hip)
 namespace {
-// Target t's cell grid and the maps' cell offsets (tnum + 1 entries); returns the widest grid.
-int depth_map_layout(const pmvs_scene* sc, int32_t* dims, int64_t* offsets) {
-  int64_t off = 0;
-  int max_gwidth = 1;
-  for (int t = 0; t < sc->ds.tnum; ++t) {
-    const int gw = (sc->hviews[t].w[sc->ds.level] + sc->ds.csize - 1) / sc->ds.csize;
-    const int gh = (sc->hviews[t].h[sc->ds.level] + sc->ds.csize - 1) / sc->ds.csize;
-    if (dims) { dims[2 * t] = gw; dims[2 * t + 1] = gh; }
-    if (offsets) offsets[t] = off;
-    off += (int64_t)gw * gh;
-    max_gwidth = std::max(max_gwidth, gw);
-  }
-  if (offsets) offsets[sc->ds.tnum] = off;
-  return max_gwidth;
+bool wants_maps(const pmvs_depthmap_buffers* b) { return b->patch || b->depth || b->normal || b->ncc; }
+
+// The four maps of `elems` cells or pixels each (the normals three floats per element).
+hipError_t stage_maps(Staging& stg, const pmvs_depthmap_buffers* b, size_t elems, DepthMapArrays* a) {
+  hipError_t e = stg.fixed(&a->patch, b->patch, elems);
+  if (e == hipSuccess) e = stg.fixed(&a->depth, b->depth, elems);
+  if (e == hipSuccess) e = stg.fixed(&a->normal, b->normal, elems * 3);
+  if (e == hipSuccess) e = stg.fixed(&a->ncc, b->ncc, elems);
+  return e;
 }
 
 // The depth maps of the device records dP[0, n).
 pmvs_status depth_maps_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, int32_t flags, const pmvs_depthmap_buffers* b) {
-  const bool dev = (flags & PMVS_EXPORT_DEVICE) != 0;
-  if (!b->patch && !b->depth && !b->normal && !b->ncc) return PMVS_OK;
+  if (!wants_maps(b)) return PMVS_OK;
   std::vector<int64_t> off((size_t)sc->ds.tnum + 1);
-  const int max_gwidth = depth_map_layout(sc, nullptr, off.data());
+  depth_map_layout(sc, nullptr, off.data());
   const size_t cells = (size_t)off.back();
-  static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "depth map array types");
-  ExportTemp tmp;
+  CallArena arena;
+  Staging stg(arena, (flags & PMVS_EXPORT_DEVICE) != 0);
   long long* d_off = nullptr;
   int* d_src = nullptr;
-  EXPCHK(tmp.alloc(&d_off, off.size()));
+  EXPCHK(arena.alloc(&d_off, off.size()));
   EXPCHK(hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice, sc->stream));
-  if ((flags & PMVS_EXPORT_WRITER_ORDER) && n > 0) {  // the export's order, from the export's code
-    EXPCHK(tmp.alloc(&d_src, (size_t)n));
-    EXPCHK(export_order(sc->ds, dP, n, max_gwidth, d_src, nullptr, nullptr, sc->stream));
-  }
+  if (pmvs_status st = writer_order_source(sc, dP, n, flags, arena, &d_src)) return st;
   DepthMapArrays a;
-  if (dev) {  // straight into the caller's device buffers
-    a.patch = b->patch; a.depth = b->depth; a.normal = b->normal; a.ncc = b->ncc;
-  } else {    // device staging for the requested arrays
-    if (b->patch) EXPCHK(tmp.alloc(&a.patch, cells));
-    if (b->depth) EXPCHK(tmp.alloc(&a.depth, cells));
-    if (b->normal) EXPCHK(tmp.alloc(&a.normal, cells * 3));
-    if (b->ncc) EXPCHK(tmp.alloc(&a.ncc, cells));
-  }
+  EXPCHK(stage_maps(stg, b, cells, &a));
   EXPCHK(depth_map_pass(sc->ds, dP, n, d_src, d_off, (long long)cells, a, sc->stream));
-  if (!dev) {
-    auto down = [&](void* dst, const void* src, size_t bytes) {
-      return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sc->stream) : hipSuccess;
-    };
-    EXPCHK(down(b->patch, a.patch, cells * sizeof(int32_t)));
-    EXPCHK(down(b->depth, a.depth, cells * sizeof(float)));
-    EXPCHK(down(b->normal, a.normal, cells * 3 * sizeof(float)));
-    EXPCHK(down(b->ncc, a.ncc, cells * sizeof(float)));
-    EXPCHK(hipStreamSynchronize(sc->stream));
-  }
+  EXPCHK(stg.finish(sc->stream));
   return PMVS_OK;
 }
 }  // namespace
@@ -1612,32 +1614,32 @@ pmvs_status pmvs_depth_map_layout(pmvs_scene* sc, int32_t* dims, int64_t* offset
 }
 
 pmvs_status pmvs_loop_depth_maps(pmvs_scene* sc, int32_t flags, const pmvs_depthmap_buffers* buffers) {
-  if (!sc || !buffers || (flags & ~(PMVS_EXPORT_WRITER_ORDER | PMVS_EXPORT_DEVICE))) return fail(PMVS_EINVAL, "invalid argument");
-  if (sc->lkept < 0) return fail(PMVS_EINVAL, "loop_depth_maps: no loop result on the device");
-  HIPCHK(hipSetDevice(sc->device));
-  return depth_maps_records(sc, sc->fpatches.p, sc->lkept, flags, buffers);
+  if (!sc || !buffers || !flags_ok(flags)) return fail(PMVS_EINVAL, "invalid argument");
+  const pmvs_patch* dP = nullptr;
+  int32_t n = 0;
+  if (pmvs_status st = loop_records(sc, "loop_depth_maps", &dP, &n)) return st;
+  return depth_maps_records(sc, dP, n, flags, buffers);
 }
 
 pmvs_status pmvs_depth_maps_patches(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, int32_t flags,
                                     const pmvs_depthmap_buffers* buffers) {
-  if (!sc || !buffers || n < 0 || (n > 0 && !patches) || (flags & ~(PMVS_EXPORT_WRITER_ORDER | PMVS_EXPORT_DEVICE)))
-    return fail(PMVS_EINVAL, "invalid argument");
-  if (pmvs_status st = check_export_patches(sc, patches, n, nullptr)) return st;
-  HIPCHK(hipSetDevice(sc->device));
-  // a buffer of its own: sc->fpatches may hold a loop result
-  ExportTemp tmp;
-  pmvs_patch* dP = nullptr;
-  if (n) {
-    EXPCHK(tmp.alloc(&dP, (size_t)n));
-    EXPCHK(hipMemcpyAsync(dP, patches, (size_t)n * sizeof(pmvs_patch), hipMemcpyHostToDevice, sc->stream));
-  }
+  if (!sc || !buffers || !records_ok(patches, n) || !flags_ok(flags)) return fail(PMVS_EINVAL, "invalid argument");
+  CallArena arena;
+  const pmvs_patch* dP = nullptr;
+  if (pmvs_status st = upload_records(sc, patches, n, nullptr, arena, &dP)) return st;
   return depth_maps_records(sc, dP, n, flags, buffers);
 }
 
 // ---- per-pixel maps (pmvs_pixmap.hip)
 namespace {
-bool pixel_range_ok(const pmvs_scene* sc, int32_t first, int32_t num) {
+bool target_range_ok(const pmvs_scene* sc, int32_t first, int32_t num) {
   return first >= 0 && num > 0 && (int64_t)first + num <= sc->ds.tnum;
+}
+bool radius_ok(int32_t radius) { return radius >= 0 && radius <= PMVS_PIXEL_MAX_RADIUS; }
+// What every call over a target range checks of the scene.  The validators below look at the scene last: a
+// call with a null argument fails before the handle is touched (the *_abi tests pass a handle that is not one).
+bool range_call_ok(const pmvs_scene* sc, int32_t flags, int32_t first, int32_t num) {
+  return sc && flags_ok(flags) && target_range_ok(sc, first, num);
 }
 
 // The images of targets [first, first + num) at the scene's level and their pixel offsets; returns the total.
@@ -1656,47 +1658,27 @@ int64_t pixel_map_layout(const pmvs_scene* sc, int32_t first, int32_t num, int32
 // The pixel maps of the device records dP[0, n).
 pmvs_status pixel_maps_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, int32_t flags, int32_t first, int32_t num,
                                int32_t radius, const pmvs_depthmap_buffers* b) {
-  const bool dev = (flags & PMVS_EXPORT_DEVICE) != 0;
-  if (!b->patch && !b->depth && !b->normal && !b->ncc) return PMVS_OK;
+  if (!wants_maps(b)) return PMVS_OK;
   const size_t pixels = (size_t)pixel_map_layout(sc, first, num, nullptr, nullptr);
-  ExportTemp tmp;
+  CallArena arena;
+  Staging stg(arena, (flags & PMVS_EXPORT_DEVICE) != 0);
   int* d_src = nullptr;
-  if ((flags & PMVS_EXPORT_WRITER_ORDER) && n > 0) {  // the export's order, from the export's code
-    EXPCHK(tmp.alloc(&d_src, (size_t)n));
-    EXPCHK(export_order(sc->ds, dP, n, depth_map_layout(sc, nullptr, nullptr), d_src, nullptr, nullptr, sc->stream));
-  }
+  if (pmvs_status st = writer_order_source(sc, dP, n, flags, arena, &d_src)) return st;
   DepthMapArrays a;
-  if (dev) {  // straight into the caller's device buffers
-    a.patch = b->patch; a.depth = b->depth; a.normal = b->normal; a.ncc = b->ncc;
-  } else {    // device staging for the requested arrays
-    if (b->patch) EXPCHK(tmp.alloc(&a.patch, pixels));
-    if (b->depth) EXPCHK(tmp.alloc(&a.depth, pixels));
-    if (b->normal) EXPCHK(tmp.alloc(&a.normal, pixels * 3));
-    if (b->ncc) EXPCHK(tmp.alloc(&a.ncc, pixels));
-  }
+  EXPCHK(stage_maps(stg, b, pixels, &a));
   EXPCHK(pixel_map_pass(sc->ds, sc->hviews.data(), dP, n, d_src, first, num, radius, a, sc->stream));
-  if (!dev) {
-    auto down = [&](void* dst, const void* src, size_t bytes) {
-      return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sc->stream) : hipSuccess;
-    };
-    EXPCHK(down(b->patch, a.patch, pixels * sizeof(int32_t)));
-    EXPCHK(down(b->depth, a.depth, pixels * sizeof(float)));
-    EXPCHK(down(b->normal, a.normal, pixels * 3 * sizeof(float)));
-    EXPCHK(down(b->ncc, a.ncc, pixels * sizeof(float)));
-    EXPCHK(hipStreamSynchronize(sc->stream));
-  }
+  EXPCHK(stg.finish(sc->stream));
   return PMVS_OK;
 }
 
 bool pixel_args_ok(const pmvs_scene* sc, int32_t flags, int32_t first, int32_t num, int32_t radius,
                    const pmvs_depthmap_buffers* b) {
-  return sc && b && !(flags & ~(PMVS_EXPORT_WRITER_ORDER | PMVS_EXPORT_DEVICE)) && pixel_range_ok(sc, first, num) &&
-         radius >= 0 && radius <= PMVS_PIXEL_MAX_RADIUS;
+  return b && radius_ok(radius) && range_call_ok(sc, flags, first, num);
 }
 }  // namespace
 
 pmvs_status pmvs_pixel_map_layout(pmvs_scene* sc, int32_t first_target, int32_t num_targets, int32_t* dims, int64_t* offsets) {
-  if (!sc || !pixel_range_ok(sc, first_target, num_targets)) return fail(PMVS_EINVAL, "invalid argument");
+  if (!sc || !target_range_ok(sc, first_target, num_targets)) return fail(PMVS_EINVAL, "invalid argument");
   pixel_map_layout(sc, first_target, num_targets, dims, offsets);
   return PMVS_OK;
 }
@@ -1704,81 +1686,58 @@ pmvs_status pmvs_pixel_map_layout(pmvs_scene* sc, int32_t first_target, int32_t 
 pmvs_status pmvs_loop_pixel_maps(pmvs_scene* sc, int32_t flags, int32_t first_target, int32_t num_targets, int32_t radius,
                                  const pmvs_depthmap_buffers* buffers) {
   if (!pixel_args_ok(sc, flags, first_target, num_targets, radius, buffers)) return fail(PMVS_EINVAL, "invalid argument");
-  if (sc->lkept < 0) return fail(PMVS_EINVAL, "loop_pixel_maps: no loop result on the device");
-  HIPCHK(hipSetDevice(sc->device));
-  return pixel_maps_records(sc, sc->fpatches.p, sc->lkept, flags, first_target, num_targets, radius, buffers);
+  const pmvs_patch* dP = nullptr;
+  int32_t n = 0;
+  if (pmvs_status st = loop_records(sc, "loop_pixel_maps", &dP, &n)) return st;
+  return pixel_maps_records(sc, dP, n, flags, first_target, num_targets, radius, buffers);
 }
 
 pmvs_status pmvs_pixel_maps_patches(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, int32_t flags, int32_t first_target,
                                     int32_t num_targets, int32_t radius, const pmvs_depthmap_buffers* buffers) {
-  if (!pixel_args_ok(sc, flags, first_target, num_targets, radius, buffers) || n < 0 || (n > 0 && !patches))
+  if (!pixel_args_ok(sc, flags, first_target, num_targets, radius, buffers) || !records_ok(patches, n))
     return fail(PMVS_EINVAL, "invalid argument");
-  if (pmvs_status st = check_export_patches(sc, patches, n, nullptr)) return st;
-  HIPCHK(hipSetDevice(sc->device));
-  // a buffer of its own: sc->fpatches may hold a loop result
-  ExportTemp tmp;
-  pmvs_patch* dP = nullptr;
-  if (n) {
-    EXPCHK(tmp.alloc(&dP, (size_t)n));
-    EXPCHK(hipMemcpyAsync(dP, patches, (size_t)n * sizeof(pmvs_patch), hipMemcpyHostToDevice, sc->stream));
-  }
+  CallArena arena;
+  const pmvs_patch* dP = nullptr;
+  if (pmvs_status st = upload_records(sc, patches, n, nullptr, arena, &dP)) return st;
   return pixel_maps_records(sc, dP, n, flags, first_target, num_targets, radius, buffers);
 }
 
 // ---- fusion of the per-pixel maps (pmvs_fuse.hip)
 namespace {
-const pmvs_depthmap_buffers kNoMaps{};  // pixel_args_ok wants a buffers pointer; the fusion's maps are scratch
-
+bool fuse_params_ok(const pmvs_fuse_params* p) {
+  return p && radius_ok(p->radius) && p->min_support >= 0 && p->min_support <= 255 && std::isfinite(p->depth_rel) &&
+         p->depth_rel >= 0.0f && !std::isnan(p->normal_cos);
+}
 bool fuse_args_ok(const pmvs_scene* sc, int32_t flags, int32_t first, int32_t num, const pmvs_fuse_params* p, int64_t cap,
                   const pmvs_fuse_buffers* b, const int64_t* count) {
-  return p && b && count && cap >= 0 && pixel_args_ok(sc, flags, first, num, p->radius, &kNoMaps) && p->min_support >= 0 &&
-         p->min_support <= 255 && std::isfinite(p->depth_rel) && p->depth_rel >= 0.0f && !std::isnan(p->normal_cos);
+  return b && count && cap >= 0 && fuse_params_ok(p) && range_call_ok(sc, flags, first, num);
 }
+
+enum { kPoints = 1, kVertices = 1, kFaces = 2 };  // Staging parts: the capped arrays that share a written count
 
 // The fusion of the device records dP[0, n).
 pmvs_status fuse_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, int32_t flags, int32_t first, int32_t num,
                          const pmvs_fuse_params* prm, int64_t cap, const pmvs_fuse_buffers* b, int64_t* count) {
-  const bool dev = (flags & PMVS_EXPORT_DEVICE) != 0;
   const size_t pixels = (size_t)pixel_map_layout(sc, first, num, nullptr, nullptr);
-  static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "fusion array types");
-  ExportTemp tmp;
+  CallArena arena;
+  Staging stg(arena, (flags & PMVS_EXPORT_DEVICE) != 0);
   int* d_src = nullptr;
-  if ((flags & PMVS_EXPORT_WRITER_ORDER) && n > 0) {  // the export's order, from the export's code
-    EXPCHK(tmp.alloc(&d_src, (size_t)n));
-    EXPCHK(export_order(sc->ds, dP, n, depth_map_layout(sc, nullptr, nullptr), d_src, nullptr, nullptr, sc->stream));
-  }
+  if (pmvs_status st = writer_order_source(sc, dP, n, flags, arena, &d_src)) return st;
   // no more points than pixels can be emitted: the staging is sized by that, whatever the caller's cap
   const size_t pts = (size_t)std::min<int64_t>(cap, (int64_t)pixels);
   FuseArrays a;
-  if (dev) {  // straight into the caller's device buffers
-    a.support_map = b->support_map; a.coord = b->coord; a.normal = b->normal; a.color = b->color; a.support = b->support;
-    a.pixel = (long long*)b->pixel; a.patch = b->patch;
-  } else {    // device staging for the requested arrays
-    if (b->support_map) EXPCHK(tmp.alloc(&a.support_map, pixels));
-    if (b->coord && pts) EXPCHK(tmp.alloc(&a.coord, pts * 3));
-    if (b->normal && pts) EXPCHK(tmp.alloc(&a.normal, pts * 3));
-    if (b->color && pts) EXPCHK(tmp.alloc(&a.color, pts * 3));
-    if (b->support && pts) EXPCHK(tmp.alloc(&a.support, pts));
-    if (b->pixel && pts) EXPCHK(tmp.alloc(&a.pixel, pts));
-    if (b->patch && pts) EXPCHK(tmp.alloc(&a.patch, pts));
-  }
+  EXPCHK(stg.fixed(&a.support_map, b->support_map, pixels));
+  EXPCHK(stg.capped(&a.coord, b->coord, pts, 3, kPoints));
+  EXPCHK(stg.capped(&a.normal, b->normal, pts, 3, kPoints));
+  EXPCHK(stg.capped(&a.color, b->color, pts, 3, kPoints));
+  EXPCHK(stg.capped(&a.support, b->support, pts, 1, kPoints));
+  EXPCHK(stg.capped(&a.pixel, b->pixel, pts, 1, kPoints));
+  EXPCHK(stg.capped(&a.patch, b->patch, pts, 1, kPoints));
   long long total = 0;
   EXPCHK(fuse_pass(sc->ds, sc->hviews.data(), dP, n, d_src, first, num, *prm, (long long)pts, a, &total, sc->stream));
   *count = total;
-  if (!dev) {
-    const size_t w = (size_t)std::min<long long>(total, (long long)cap);  // the points written
-    auto down = [&](void* dst, const void* src, size_t bytes) {
-      return (dst && src && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sc->stream) : hipSuccess;
-    };
-    EXPCHK(down(b->support_map, a.support_map, pixels));
-    EXPCHK(down(b->coord, a.coord, w * 3 * sizeof(float)));
-    EXPCHK(down(b->normal, a.normal, w * 3 * sizeof(float)));
-    EXPCHK(down(b->color, a.color, w * 3));
-    EXPCHK(down(b->support, a.support, w));
-    EXPCHK(down(b->pixel, a.pixel, w * sizeof(int64_t)));
-    EXPCHK(down(b->patch, a.patch, w * sizeof(int32_t)));
-    EXPCHK(hipStreamSynchronize(sc->stream));
-  }
+  stg.wrote(kPoints, (size_t)total);
+  EXPCHK(stg.finish(sc->stream));
   return PMVS_OK;
 }
 }  // namespace
@@ -1786,33 +1745,25 @@ pmvs_status fuse_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, int32_
 pmvs_status pmvs_loop_fuse(pmvs_scene* sc, int32_t flags, int32_t first_target, int32_t num_targets,
                            const pmvs_fuse_params* params, int64_t cap, const pmvs_fuse_buffers* buffers, int64_t* count) {
   if (!fuse_args_ok(sc, flags, first_target, num_targets, params, cap, buffers, count)) return fail(PMVS_EINVAL, "invalid argument");
-  if (sc->lkept < 0) return fail(PMVS_EINVAL, "loop_fuse: no loop result on the device");
-  HIPCHK(hipSetDevice(sc->device));
-  return fuse_records(sc, sc->fpatches.p, sc->lkept, flags, first_target, num_targets, params, cap, buffers, count);
+  const pmvs_patch* dP = nullptr;
+  int32_t n = 0;
+  if (pmvs_status st = loop_records(sc, "loop_fuse", &dP, &n)) return st;
+  return fuse_records(sc, dP, n, flags, first_target, num_targets, params, cap, buffers, count);
 }
 
 pmvs_status pmvs_fuse_patches(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, int32_t flags, int32_t first_target,
                               int32_t num_targets, const pmvs_fuse_params* params, int64_t cap, const pmvs_fuse_buffers* buffers,
                               int64_t* count) {
-  if (!fuse_args_ok(sc, flags, first_target, num_targets, params, cap, buffers, count) || n < 0 || (n > 0 && !patches))
+  if (!fuse_args_ok(sc, flags, first_target, num_targets, params, cap, buffers, count) || !records_ok(patches, n))
     return fail(PMVS_EINVAL, "invalid argument");
-  if (pmvs_status st = check_export_patches(sc, patches, n, nullptr)) return st;
-  HIPCHK(hipSetDevice(sc->device));
-  // a buffer of its own: sc->fpatches may hold a loop result
-  ExportTemp tmp;
-  pmvs_patch* dP = nullptr;
-  if (n) {
-    EXPCHK(tmp.alloc(&dP, (size_t)n));
-    EXPCHK(hipMemcpyAsync(dP, patches, (size_t)n * sizeof(pmvs_patch), hipMemcpyHostToDevice, sc->stream));
-  }
+  CallArena arena;
+  const pmvs_patch* dP = nullptr;
+  if (pmvs_status st = upload_records(sc, patches, n, nullptr, arena, &dP)) return st;
   return fuse_records(sc, dP, n, flags, first_target, num_targets, params, cap, buffers, count);
 }
 
 // ---- meshing of the fused maps (pmvs_mesh.hip)
 namespace {
-const pmvs_fuse_buffers kNoCloud{};  // fuse_args_ok wants buffers and a count; the meshing emits no cloud
-const int64_t kNoCount = 0;
-
 bool volume_ok(const pmvs_volume* v) {
   if (!v || !std::isfinite(v->origin[0]) || !std::isfinite(v->origin[1]) || !std::isfinite(v->origin[2])) return false;
   if (!std::isfinite(v->voxel) || !(v->voxel > 0.0f)) return false;
@@ -1820,10 +1771,13 @@ bool volume_ok(const pmvs_volume* v) {
   return (int64_t)v->dims[0] * v->dims[1] <= INT32_MAX && (int64_t)v->dims[0] * v->dims[1] * v->dims[2] <= INT32_MAX;
 }
 
+bool tsdf_params_ok(const pmvs_tsdf_params* p) {
+  return p && fuse_params_ok(&p->fuse) && std::isfinite(p->trunc) && p->trunc > 0.0f;
+}
+
 bool tsdf_args_ok(const pmvs_scene* sc, int32_t flags, int32_t first, int32_t num, const pmvs_tsdf_params* p,
                   const pmvs_volume* v) {
-  return p && fuse_args_ok(sc, flags, first, num, &p->fuse, 0, &kNoCloud, &kNoCount) && std::isfinite(p->trunc) &&
-         p->trunc > 0.0f && volume_ok(v);
+  return tsdf_params_ok(p) && volume_ok(v) && range_call_ok(sc, flags, first, num);
 }
 
 bool mesh_args_ok(int32_t min_obs, int64_t vcap, int64_t fcap, const pmvs_mesh_buffers* b, const int64_t* nverts,
@@ -1835,12 +1789,9 @@ size_t volume_voxels(const pmvs_volume& v) { return (size_t)v.dims[0] * v.dims[1
 
 // The fusion's maps and pass flags of the device records dP[0, n) into `f`, enqueued on the scene's stream.
 pmvs_status tsdf_maps(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, int32_t flags, int32_t first, int32_t num,
-                      const pmvs_fuse_params& prm, ExportTemp& tmp, FuseMaps& f) {
+                      const pmvs_fuse_params& prm, CallArena& arena, FuseMaps& f) {
   int* d_src = nullptr;
-  if ((flags & PMVS_EXPORT_WRITER_ORDER) && n > 0) {  // the export's order, from the export's code
-    EXPCHK(tmp.alloc(&d_src, (size_t)n));
-    EXPCHK(export_order(sc->ds, dP, n, depth_map_layout(sc, nullptr, nullptr), d_src, nullptr, nullptr, sc->stream));
-  }
+  if (pmvs_status st = writer_order_source(sc, dP, n, flags, arena, &d_src)) return st;
   EXPCHK(fuse_maps_pass(sc->ds, sc->hviews.data(), dP, n, d_src, first, num, prm, nullptr, f, sc->stream));
   return PMVS_OK;
 }
@@ -1848,30 +1799,18 @@ pmvs_status tsdf_maps(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, int32_t f
 // The TSDF of the device records dP[0, n).
 pmvs_status tsdf_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, int32_t flags, int32_t first, int32_t num,
                          const pmvs_tsdf_params* prm, const pmvs_volume* vol, const pmvs_tsdf_buffers* b) {
-  const bool dev = (flags & PMVS_EXPORT_DEVICE) != 0;
   if (!b->tsdf && !b->obs && !b->color) return PMVS_OK;
   const size_t voxels = volume_voxels(*vol);
-  ExportTemp tmp;
+  CallArena arena;
+  Staging stg(arena, (flags & PMVS_EXPORT_DEVICE) != 0);
   FuseMaps f;
   TsdfArrays a;
-  if (dev) {  // straight into the caller's device buffers
-    a.tsdf = b->tsdf; a.obs = b->obs; a.color = b->color;
-  } else {    // device staging for the requested arrays
-    if (b->tsdf) EXPCHK(tmp.alloc(&a.tsdf, voxels));
-    if (b->obs) EXPCHK(tmp.alloc(&a.obs, voxels));
-    if (b->color) EXPCHK(tmp.alloc(&a.color, voxels * 4));
-  }
-  if (pmvs_status st = tsdf_maps(sc, dP, n, flags, first, num, prm->fuse, tmp, f)) return st;
+  EXPCHK(stg.fixed(&a.tsdf, b->tsdf, voxels));
+  EXPCHK(stg.fixed(&a.obs, b->obs, voxels));
+  EXPCHK(stg.fixed(&a.color, b->color, voxels * 4));
+  if (pmvs_status st = tsdf_maps(sc, dP, n, flags, first, num, prm->fuse, arena, f)) return st;
   EXPCHK(tsdf_integrate(sc->ds, f, first, num, *vol, prm->trunc, a, sc->stream));
-  if (!dev) {
-    auto down = [&](void* dst, const void* src, size_t bytes) {
-      return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sc->stream) : hipSuccess;
-    };
-    EXPCHK(down(b->tsdf, a.tsdf, voxels * sizeof(float)));
-    EXPCHK(down(b->obs, a.obs, voxels));
-    EXPCHK(down(b->color, a.color, voxels * 4));
-  }
-  EXPCHK(hipStreamSynchronize(sc->stream));  // the maps are freed on return
+  EXPCHK(stg.finish(sc->stream, true));  // in device mode too: the maps are freed on return
   return PMVS_OK;
 }
 
@@ -1883,31 +1822,20 @@ pmvs_status mesh_device_volume(pmvs_scene* sc, bool dev, const pmvs_volume* vol,
   const size_t cells = (size_t)(vol->dims[0] - 1) * (vol->dims[1] - 1) * (vol->dims[2] - 1);
   // no more vertices than cells and no more faces than 6 per voxel exist: the staging is sized by that
   const size_t nv = (size_t)std::min<int64_t>(vcap, (int64_t)cells), nf = (size_t)std::min<int64_t>(fcap, (int64_t)voxels * 6);
-  ExportTemp tmp;
+  CallArena arena;
+  Staging stg(arena, dev);
   MeshArrays a;
-  if (dev) {
-    a.vertex = b->vertex; a.normal = b->normal; a.color = b->color; a.face = b->face;
-  } else {
-    if (b->vertex && nv) EXPCHK(tmp.alloc(&a.vertex, nv * 3));
-    if (b->normal && nv) EXPCHK(tmp.alloc(&a.normal, nv * 3));
-    if (b->color && nv) EXPCHK(tmp.alloc(&a.color, nv * 3));
-    if (b->face && nf) EXPCHK(tmp.alloc(&a.face, nf * 3));
-  }
+  EXPCHK(stg.capped(&a.vertex, b->vertex, nv, 3, kVertices));
+  EXPCHK(stg.capped(&a.normal, b->normal, nv, 3, kVertices));
+  EXPCHK(stg.capped(&a.color, b->color, nv, 3, kVertices));
+  EXPCHK(stg.capped(&a.face, b->face, nf, 3, kFaces));
   long long tv = 0, tf = 0;
   EXPCHK(tsdf_mesh_pass(*vol, min_obs, d_tsdf, d_obs, d_color, (long long)nv, (long long)nf, a, &tv, &tf, sc->stream));
   *nverts = tv;
   *nfaces = tf;
-  if (!dev) {
-    const size_t wv = (size_t)std::min<long long>(tv, (long long)nv), wf = (size_t)std::min<long long>(tf, (long long)nf);
-    auto down = [&](void* dst, const void* src, size_t bytes) {
-      return (dst && src && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sc->stream) : hipSuccess;
-    };
-    EXPCHK(down(b->vertex, a.vertex, wv * 3 * sizeof(float)));
-    EXPCHK(down(b->normal, a.normal, wv * 3 * sizeof(float)));
-    EXPCHK(down(b->color, a.color, wv * 3));
-    EXPCHK(down(b->face, a.face, wf * 3 * sizeof(int32_t)));
-    EXPCHK(hipStreamSynchronize(sc->stream));
-  }
+  stg.wrote(kVertices, (size_t)tv);
+  stg.wrote(kFaces, (size_t)tf);
+  EXPCHK(stg.finish(sc->stream));
   return PMVS_OK;
 }
 
@@ -1916,72 +1844,61 @@ pmvs_status mesh_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, int32_
                          const pmvs_tsdf_params* prm, const pmvs_volume* vol, int32_t min_obs, int64_t vcap, int64_t fcap,
                          const pmvs_mesh_buffers* b, int64_t* nverts, int64_t* nfaces) {
   const size_t voxels = volume_voxels(*vol);
-  ExportTemp tmp;
+  CallArena arena;
   TsdfArrays a;
-  EXPCHK(tmp.alloc(&a.tsdf, voxels));
-  EXPCHK(tmp.alloc(&a.obs, voxels));
-  EXPCHK(tmp.alloc(&a.color, voxels * 4));
+  EXPCHK(arena.alloc(&a.tsdf, voxels));
+  EXPCHK(arena.alloc(&a.obs, voxels));
+  EXPCHK(arena.alloc(&a.color, voxels * 4));
   {
     FuseMaps f;
-    if (pmvs_status st = tsdf_maps(sc, dP, n, flags, first, num, prm->fuse, tmp, f)) return st;
+    if (pmvs_status st = tsdf_maps(sc, dP, n, flags, first, num, prm->fuse, arena, f)) return st;
     EXPCHK(tsdf_integrate(sc->ds, f, first, num, *vol, prm->trunc, a, sc->stream));
     EXPCHK(hipStreamSynchronize(sc->stream));  // the maps are freed here, before the extraction's scratch
   }
   return mesh_device_volume(sc, (flags & PMVS_EXPORT_DEVICE) != 0, vol, min_obs, a.tsdf, a.obs, a.color, vcap, fcap, b, nverts,
                             nfaces);
 }
-
-// The records of a _patches call on the device (a buffer of its own: sc->fpatches may hold a loop result).
-pmvs_status upload_records(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, ExportTemp& tmp, pmvs_patch** dP) {
-  *dP = nullptr;
-  if (n) {
-    EXPCHK(tmp.alloc(dP, (size_t)n));
-    EXPCHK(hipMemcpyAsync(*dP, patches, (size_t)n * sizeof(pmvs_patch), hipMemcpyHostToDevice, sc->stream));
-  }
-  return PMVS_OK;
-}
 }  // namespace
 
 pmvs_status pmvs_loop_tsdf(pmvs_scene* sc, int32_t flags, int32_t first_target, int32_t num_targets,
                            const pmvs_tsdf_params* params, const pmvs_volume* volume, const pmvs_tsdf_buffers* buffers) {
   if (!buffers || !tsdf_args_ok(sc, flags, first_target, num_targets, params, volume)) return fail(PMVS_EINVAL, "invalid argument");
-  if (sc->lkept < 0) return fail(PMVS_EINVAL, "loop_tsdf: no loop result on the device");
-  HIPCHK(hipSetDevice(sc->device));
-  return tsdf_records(sc, sc->fpatches.p, sc->lkept, flags, first_target, num_targets, params, volume, buffers);
+  const pmvs_patch* dP = nullptr;
+  int32_t n = 0;
+  if (pmvs_status st = loop_records(sc, "loop_tsdf", &dP, &n)) return st;
+  return tsdf_records(sc, dP, n, flags, first_target, num_targets, params, volume, buffers);
 }
 
 pmvs_status pmvs_tsdf_patches(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, int32_t flags, int32_t first_target,
                               int32_t num_targets, const pmvs_tsdf_params* params, const pmvs_volume* volume,
                               const pmvs_tsdf_buffers* buffers) {
-  if (!buffers || !tsdf_args_ok(sc, flags, first_target, num_targets, params, volume) || n < 0 || (n > 0 && !patches))
+  if (!buffers || !tsdf_args_ok(sc, flags, first_target, num_targets, params, volume) || !records_ok(patches, n))
     return fail(PMVS_EINVAL, "invalid argument");
-  if (pmvs_status st = check_export_patches(sc, patches, n, nullptr)) return st;
-  HIPCHK(hipSetDevice(sc->device));
-  ExportTemp tmp;
-  pmvs_patch* dP = nullptr;
-  if (pmvs_status st = upload_records(sc, patches, n, tmp, &dP)) return st;
+  CallArena arena;
+  const pmvs_patch* dP = nullptr;
+  if (pmvs_status st = upload_records(sc, patches, n, nullptr, arena, &dP)) return st;
   return tsdf_records(sc, dP, n, flags, first_target, num_targets, params, volume, buffers);
 }
 
 pmvs_status pmvs_tsdf_mesh(pmvs_scene* sc, int32_t flags, const pmvs_volume* volume, int32_t min_obs, const float* tsdf,
                            const uint8_t* obs, const uint8_t* color, int64_t vcap, int64_t fcap, const pmvs_mesh_buffers* buffers,
                            int64_t* nverts, int64_t* nfaces) {
-  if (!sc || (flags & ~PMVS_EXPORT_DEVICE) || !volume_ok(volume) || !tsdf || !obs ||
+  if (!sc || !flags_ok(flags, PMVS_EXPORT_DEVICE) || !volume_ok(volume) || !tsdf || !obs ||
       !mesh_args_ok(min_obs, vcap, fcap, buffers, nverts, nfaces))
     return fail(PMVS_EINVAL, "invalid argument");
   HIPCHK(hipSetDevice(sc->device));
   const bool dev = (flags & PMVS_EXPORT_DEVICE) != 0;
-  ExportTemp tmp;
+  CallArena arena;
   if (!dev) {  // the volume goes up
     const size_t voxels = volume_voxels(*volume);
     float* d_tsdf = nullptr;
     uint8_t *d_obs = nullptr, *d_color = nullptr;
-    EXPCHK(tmp.alloc(&d_tsdf, voxels));
-    EXPCHK(tmp.alloc(&d_obs, voxels));
+    EXPCHK(arena.alloc(&d_tsdf, voxels));
+    EXPCHK(arena.alloc(&d_obs, voxels));
     EXPCHK(hipMemcpyAsync(d_tsdf, tsdf, voxels * sizeof(float), hipMemcpyHostToDevice, sc->stream));
     EXPCHK(hipMemcpyAsync(d_obs, obs, voxels, hipMemcpyHostToDevice, sc->stream));
     if (color) {
-      EXPCHK(tmp.alloc(&d_color, voxels * 4));
+      EXPCHK(arena.alloc(&d_color, voxels * 4));
       EXPCHK(hipMemcpyAsync(d_color, color, voxels * 4, hipMemcpyHostToDevice, sc->stream));
     }
     tsdf = d_tsdf, obs = d_obs, color = d_color;
@@ -1994,34 +1911,32 @@ pmvs_status pmvs_tsdf_mesh(pmvs_scene* sc, int32_t flags, const pmvs_volume* vol
 pmvs_status pmvs_loop_mesh(pmvs_scene* sc, int32_t flags, int32_t first_target, int32_t num_targets,
                            const pmvs_tsdf_params* params, const pmvs_volume* volume, int32_t min_obs, int64_t vcap, int64_t fcap,
                            const pmvs_mesh_buffers* buffers, int64_t* nverts, int64_t* nfaces) {
-  if (!tsdf_args_ok(sc, flags, first_target, num_targets, params, volume) ||
-      !mesh_args_ok(min_obs, vcap, fcap, buffers, nverts, nfaces))
+  if (!mesh_args_ok(min_obs, vcap, fcap, buffers, nverts, nfaces) ||
+      !tsdf_args_ok(sc, flags, first_target, num_targets, params, volume))
     return fail(PMVS_EINVAL, "invalid argument");
-  if (sc->lkept < 0) return fail(PMVS_EINVAL, "loop_mesh: no loop result on the device");
-  HIPCHK(hipSetDevice(sc->device));
-  return mesh_records(sc, sc->fpatches.p, sc->lkept, flags, first_target, num_targets, params, volume, min_obs, vcap, fcap,
-                      buffers, nverts, nfaces);
+  const pmvs_patch* dP = nullptr;
+  int32_t n = 0;
+  if (pmvs_status st = loop_records(sc, "loop_mesh", &dP, &n)) return st;
+  return mesh_records(sc, dP, n, flags, first_target, num_targets, params, volume, min_obs, vcap, fcap, buffers, nverts, nfaces);
 }
 
 pmvs_status pmvs_mesh_patches(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, int32_t flags, int32_t first_target,
                               int32_t num_targets, const pmvs_tsdf_params* params, const pmvs_volume* volume, int32_t min_obs,
                               int64_t vcap, int64_t fcap, const pmvs_mesh_buffers* buffers, int64_t* nverts, int64_t* nfaces) {
-  if (!tsdf_args_ok(sc, flags, first_target, num_targets, params, volume) ||
-      !mesh_args_ok(min_obs, vcap, fcap, buffers, nverts, nfaces) || n < 0 || (n > 0 && !patches))
+  if (!mesh_args_ok(min_obs, vcap, fcap, buffers, nverts, nfaces) || !records_ok(patches, n) ||
+      !tsdf_args_ok(sc, flags, first_target, num_targets, params, volume))
     return fail(PMVS_EINVAL, "invalid argument");
-  if (pmvs_status st = check_export_patches(sc, patches, n, nullptr)) return st;
-  HIPCHK(hipSetDevice(sc->device));
-  ExportTemp tmp;
-  pmvs_patch* dP = nullptr;
-  if (pmvs_status st = upload_records(sc, patches, n, tmp, &dP)) return st;
+  CallArena arena;
+  const pmvs_patch* dP = nullptr;
+  if (pmvs_status st = upload_records(sc, patches, n, nullptr, arena, &dP)) return st;
   return mesh_records(sc, dP, n, flags, first_target, num_targets, params, volume, min_obs, vcap, fcap, buffers, nverts, nfaces);
 }
 
 // ---- text files (pmvs_text.hip)
 namespace {
 bool text_args_ok(const pmvs_scene* sc, int32_t kind, int32_t flags, const char* out, int64_t cap, const int64_t* bytes) {
-  return sc && bytes && (kind == PMVS_TEXT_PLY || kind == PMVS_TEXT_PATCH || kind == PMVS_TEXT_PSET) &&
-         !(flags & ~(PMVS_EXPORT_WRITER_ORDER | PMVS_EXPORT_DEVICE)) && cap >= 0 && (out || cap == 0);
+  return sc && bytes && (kind == PMVS_TEXT_PLY || kind == PMVS_TEXT_PATCH || kind == PMVS_TEXT_PSET) && flags_ok(flags) &&
+         cap >= 0 && (out || cap == 0);
 }
 
 // The header of a `kind` file of n patches (pmvs_io.cpp's writers).
@@ -2040,7 +1955,8 @@ pmvs_status text_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, const 
                          int32_t flags, const int32_t* index2image, char* out, int64_t cap, int64_t* bytes) {
   const bool dev = (flags & PMVS_EXPORT_DEVICE) != 0;
   const std::string header = text_header(kind, n);
-  ExportTemp tmp;
+  CallArena arena;
+  Staging stg(arena, dev);
   TextArrays t;
   long long* d_off = nullptr;
   int64_t total = (int64_t)header.size();
@@ -2048,24 +1964,21 @@ pmvs_status text_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, const 
     // the export's arrays this kind reads, into call-scoped scratch
     const size_t np = (size_t)n;
     ExportArrays a;
-    EXPCHK(tmp.alloc(&a.fields, np * 11));
-    if (kind == PMVS_TEXT_PLY) EXPCHK(tmp.alloc(&a.colors, np * 3));
+    EXPCHK(arena.alloc(&a.fields, np * 11));
+    if (kind == PMVS_TEXT_PLY) EXPCHK(arena.alloc(&a.colors, np * 3));
     if (kind == PMVS_TEXT_PATCH) {
-      EXPCHK(tmp.alloc(&a.image_off, np + 1));
-      EXPCHK(tmp.alloc(&a.image_ids, (size_t)sz.image_entries));
-      EXPCHK(tmp.alloc(&a.vimage_off, np + 1));
-      EXPCHK(tmp.alloc(&a.vimage_ids, (size_t)sz.vimage_entries));
+      EXPCHK(arena.alloc(&a.image_off, np + 1));
+      EXPCHK(arena.alloc(&a.image_ids, (size_t)sz.image_entries));
+      EXPCHK(arena.alloc(&a.vimage_off, np + 1));
+      EXPCHK(arena.alloc(&a.vimage_ids, (size_t)sz.vimage_entries));
     }
     int* d_tab = nullptr;
-    if (index2image && kind == PMVS_TEXT_PATCH) {
-      EXPCHK(tmp.alloc(&d_tab, (size_t)sc->ds.num));
-      EXPCHK(hipMemcpyAsync(d_tab, index2image, (size_t)sc->ds.num * sizeof(int), hipMemcpyHostToDevice, sc->stream));
-    }
+    if (pmvs_status st = upload_index2image(sc, kind == PMVS_TEXT_PATCH ? index2image : nullptr, arena, &d_tab)) return st;
     const int max_gwidth = depth_map_layout(sc, nullptr, nullptr);
     EXPCHK(export_pass(sc->ds, dP, n, (flags & PMVS_EXPORT_WRITER_ORDER) != 0, max_gwidth, d_tab, a, sc->stream));
     t.fields = a.fields; t.colors = a.colors; t.image_off = a.image_off; t.image_ids = a.image_ids;
     t.vimage_off = a.vimage_off; t.vimage_ids = a.vimage_ids;
-    EXPCHK(tmp.alloc(&d_off, np + 1));
+    EXPCHK(arena.alloc(&d_off, np + 1));
     EXPCHK(text_offsets(kind, t, n, (long long)header.size(), d_off, sc->stream));
     long long end = 0;
     EXPCHK(hipMemcpyAsync(&end, d_off + n, sizeof(end), hipMemcpyDeviceToHost, sc->stream));
@@ -2076,19 +1989,16 @@ pmvs_status text_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, const 
   if (!out && cap == 0) return PMVS_OK;  // the size query
   if (cap < total) return fail(PMVS_EINVAL, "text: the buffer holds %lld bytes, the text has %lld", (long long)cap, (long long)total);
   if (total == 0) return PMVS_OK;
-  char* d_out = out;
-  if (!dev) {
-    if (n == 0) {
-      std::memcpy(out, header.data(), header.size());
-      return PMVS_OK;
-    }
-    EXPCHK(tmp.alloc(&d_out, (size_t)total));
+  if (!dev && n == 0) {
+    std::memcpy(out, header.data(), header.size());
+    return PMVS_OK;
   }
+  char* d_out = nullptr;
+  EXPCHK(stg.fixed(&d_out, out, (size_t)total));
   if (!header.empty()) EXPCHK(hipMemcpyAsync(d_out, header.data(), header.size(), hipMemcpyHostToDevice, sc->stream));
   EXPCHK(text_write(kind, t, n, d_off, d_out, sc->stream));
-  if (!dev) EXPCHK(hipMemcpyAsync(out, d_out, (size_t)total, hipMemcpyDeviceToHost, sc->stream));
-  // the scratch and the header are freed on return: the work that reads them must have finished
-  EXPCHK(hipStreamSynchronize(sc->stream));
+  // in device mode too: the scratch and the header are freed on return, the work that reads them must have finished
+  EXPCHK(stg.finish(sc->stream, true));
   return PMVS_OK;
 }
 }  // namespace
@@ -2096,27 +2006,21 @@ pmvs_status text_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, const 
 pmvs_status pmvs_loop_text(pmvs_scene* sc, int32_t kind, int32_t flags, const int32_t* index2image, char* out,
                            int64_t cap, int64_t* bytes) {
   if (!text_args_ok(sc, kind, flags, out, cap, bytes)) return fail(PMVS_EINVAL, "invalid argument");
-  if (sc->lkept < 0) return fail(PMVS_EINVAL, "loop_text: no loop result on the device");
-  HIPCHK(hipSetDevice(sc->device));
+  const pmvs_patch* dP = nullptr;
+  int32_t n = 0;
+  if (pmvs_status st = loop_records(sc, "loop_text", &dP, &n)) return st;
   pmvs_export_sizes sz{};
-  if (pmvs_status st = device_export_sizes(sc, sc->fpatches.p, sc->lkept, &sz)) return st;
-  return text_records(sc, sc->fpatches.p, sc->lkept, sz, kind, flags, index2image, out, cap, bytes);
+  if (pmvs_status st = device_export_sizes(sc, dP, n, &sz)) return st;
+  return text_records(sc, dP, n, sz, kind, flags, index2image, out, cap, bytes);
 }
 
 pmvs_status pmvs_text_patches(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, int32_t kind, int32_t flags,
                               const int32_t* index2image, char* out, int64_t cap, int64_t* bytes) {
-  if (!text_args_ok(sc, kind, flags, out, cap, bytes) || n < 0 || (n > 0 && !patches))
-    return fail(PMVS_EINVAL, "invalid argument");
+  if (!text_args_ok(sc, kind, flags, out, cap, bytes) || !records_ok(patches, n)) return fail(PMVS_EINVAL, "invalid argument");
+  CallArena arena;
+  const pmvs_patch* dP = nullptr;
   pmvs_export_sizes sz{};
-  if (pmvs_status st = check_export_patches(sc, patches, n, &sz)) return st;
-  HIPCHK(hipSetDevice(sc->device));
-  // a buffer of its own: sc->fpatches may hold a loop result
-  ExportTemp tmp;
-  pmvs_patch* dP = nullptr;
-  if (n) {
-    EXPCHK(tmp.alloc(&dP, (size_t)n));
-    EXPCHK(hipMemcpyAsync(dP, patches, (size_t)n * sizeof(pmvs_patch), hipMemcpyHostToDevice, sc->stream));
-  }
+  if (pmvs_status st = upload_records(sc, patches, n, &sz, arena, &dP)) return st;
   return text_records(sc, dP, n, sz, kind, flags, index2image, out, cap, bytes);
 }
 
@@ -2128,13 +2032,13 @@ pmvs_status pmvs_selftest_format(int32_t device, int32_t precision, const float*
     return PMVS_OK;
   }
   HIPCHK(hipSetDevice(device));
-  ExportTemp tmp;
+  CallArena arena;
   float* d_in = nullptr;
   char* d_out = nullptr;
   int* d_len = nullptr;
-  EXPCHK(tmp.alloc(&d_in, (size_t)n));
-  EXPCHK(tmp.alloc(&d_out, (size_t)n * 24));
-  EXPCHK(tmp.alloc(&d_len, (size_t)n));
+  EXPCHK(arena.alloc(&d_in, (size_t)n));
+  EXPCHK(arena.alloc(&d_out, (size_t)n * 24));
+  EXPCHK(arena.alloc(&d_len, (size_t)n));
   EXPCHK(hipMemcpy(d_in, in, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
   EXPCHK(hipMemset(d_out, 0, (size_t)n * 24));
   EXPCHK(launch_format_selftest(precision, d_in, n, d_out, d_len, nullptr));

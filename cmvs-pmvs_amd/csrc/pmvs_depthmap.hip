@@ -101,16 +101,6 @@ __global__ __launch_bounds__(256) void depthmap_resolve_kernel(const unsigned lo
   }
 }
 
-struct DevMem {  // device scratch of one call
-  void* p = nullptr;
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-  template <class T>
-  T* as() const { return static_cast<T*>(p); }
-  ~DevMem() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 inline hipError_t blocks_for(long long items, unsigned* blocks) {
   const long long g = (items + 255) / 256;
   if (g > INT_MAX) return hipErrorInvalidValue;
@@ -132,23 +122,23 @@ hipError_t depth_map_pass(const DScene& s, const pmvs_patch* P, int n, const int
                           long long cells, const DepthMapArrays& out, hipStream_t st) {
   if (cells <= 0 || !(out.patch || out.depth || out.normal || out.ncc)) return hipSuccess;
   const bool attr = out.normal || out.ncc;
-  DevMem keys, coordc, attrc;
+  DevBuf<unsigned long long> keys;
+  DevBuf<float4> coordc, attrc;
   unsigned nb = 0;
-  DCHK(keys.alloc((size_t)cells * sizeof(unsigned long long)));
+  DCHK(keys.alloc((size_t)cells));
   DCHK(hipMemsetAsync(keys.p, 0xff, (size_t)cells * sizeof(unsigned long long), st));
   if (n > 0) {
-    DCHK(coordc.alloc((size_t)n * sizeof(float4)));
-    if (attr) DCHK(attrc.alloc((size_t)n * sizeof(float4)));
-    DCHK(depth_map_pack(P, src, n, coordc.as<float4>(), attr ? attrc.as<float4>() : nullptr, st));
+    DCHK(coordc.alloc((size_t)n));
+    if (attr) DCHK(attrc.alloc((size_t)n));
+    DCHK(depth_map_pack(P, src, n, coordc.p, attrc.p, st));
     const int ngrp = (s.tnum + kTargetsPerThread - 1) / kTargetsPerThread;
     DCHK(blocks_for((long long)n * ngrp, &nb));
-    hipLaunchKernelGGL(depthmap_build_kernel, dim3(nb), dim3(256), 0, st, s, coordc.as<float4>(), n, d_off,
-                       keys.as<unsigned long long>());
+    hipLaunchKernelGGL(depthmap_build_kernel, dim3(nb), dim3(256), 0, st, s, coordc.p, n, d_off, keys.p);
     DCHK(hipGetLastError());
   }
   DCHK(blocks_for(cells, &nb));
-  hipLaunchKernelGGL(depthmap_resolve_kernel, dim3(nb), dim3(256), 0, st, keys.as<unsigned long long>(), cells,
-                     attrc.as<float4>(), out.patch, out.depth, out.normal, out.ncc);
+  hipLaunchKernelGGL(depthmap_resolve_kernel, dim3(nb), dim3(256), 0, st, keys.p, cells, attrc.p, out.patch, out.depth,
+                     out.normal, out.ncc);
   DCHK(hipGetLastError());
   // the scratch above is freed on return: the work that reads it must have finished
   return hipStreamSynchronize(st);

@@ -178,16 +178,6 @@ __global__ __launch_bounds__(256) void export_gather_kernel(DScene s, const pmvs
   }
 }
 
-struct DevMem {  // device scratch of one export call
-  void* p = nullptr;
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-  template <class T>
-  T* as() const { return static_cast<T*>(p); }
-  ~DevMem() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 inline int grid_for(long long items, int per_block) {
   const long long g = (items + per_block - 1) / per_block;
   return (int)(g < 1 ? 1 : (g > (1 << 20) ? (1 << 20) : g));
@@ -212,21 +202,21 @@ hipError_t export_order(const DScene& s, const pmvs_patch* P, int n, int max_gwi
   int cell_bits = 1, end_bit;
   while ((1LL << cell_bits) < 2 * bias) ++cell_bits;
   for (end_bit = cell_bits; ((long long)s.tnum >> (end_bit - cell_bits)) != 0; ++end_bit) {}
-  DevMem keys, keys2, idx, temp;
+  DevBuf<unsigned long long> keys, keys2;
+  DevBuf<int> idx;
+  DevBuf<char> temp;
   size_t tb_sort = 0;
-  XCHK(keys.alloc(n * sizeof(unsigned long long)));
-  XCHK(keys2.alloc(n * sizeof(unsigned long long)));
-  XCHK(idx.alloc(n * sizeof(int)));
-  XCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, keys.as<unsigned long long>(), keys2.as<unsigned long long>(),
-                                          idx.as<int>(), sorted, n, 0, end_bit, st));
+  XCHK(keys.alloc(n));
+  XCHK(keys2.alloc(n));
+  XCHK(idx.alloc(n));
+  XCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, keys.p, keys2.p, idx.p, sorted, n, 0, end_bit, st));
   XCHK(temp.alloc(tb_sort));
-  hipLaunchKernelGGL(export_key_kernel, dim3(grid_for(n, 256 / kKeyLanes)), dim3(256), 0, st, s, P, n, cell_bits, bias,
-                     keys.as<unsigned long long>(), cnt_i, cnt_v);
+  hipLaunchKernelGGL(export_key_kernel, dim3(grid_for(n, 256 / kKeyLanes)), dim3(256), 0, st, s, P, n, cell_bits, bias, keys.p,
+                     cnt_i, cnt_v);
   XCHK(hipGetLastError());
-  hipLaunchKernelGGL(export_iota_kernel, dim3(grid_for(n, 256)), dim3(256), 0, st, idx.as<int>(), n);
+  hipLaunchKernelGGL(export_iota_kernel, dim3(grid_for(n, 256)), dim3(256), 0, st, idx.p, n);
   XCHK(hipGetLastError());
-  XCHK(hipcub::DeviceRadixSort::SortPairs(temp.p, tb_sort, keys.as<unsigned long long>(), keys2.as<unsigned long long>(),
-                                          idx.as<int>(), sorted, n, 0, end_bit, st));
+  XCHK(hipcub::DeviceRadixSort::SortPairs(temp.p, tb_sort, keys.p, keys2.p, idx.p, sorted, n, 0, end_bit, st));
   // the scratch above is freed on return: the work that reads it must have finished
   return hipStreamSynchronize(st);
 }
@@ -235,46 +225,48 @@ hipError_t export_pass(const DScene& s, const pmvs_patch* P, int n, bool writer_
                        const ExportArrays& out, hipStream_t st) {
   if (n <= 0) return hipSuccess;
   const size_t n1 = (size_t)n + 1;
-  DevMem cnt_i, cnt_v, c64_i, c64_v, off_i, off_v, idx2, temp;
-  XCHK(cnt_i.alloc(n * sizeof(int)));
-  XCHK(cnt_v.alloc(n * sizeof(int)));
-  XCHK(c64_i.alloc(n1 * sizeof(long long)));
-  XCHK(c64_v.alloc(n1 * sizeof(long long)));
+  DevBuf<int> cnt_i, cnt_v, idx2;
+  DevBuf<long long> c64_i, c64_v, off_i, off_v;
+  DevBuf<char> temp;
+  XCHK(cnt_i.alloc(n));
+  XCHK(cnt_v.alloc(n));
+  XCHK(c64_i.alloc(n1));
+  XCHK(c64_v.alloc(n1));
   long long *ioff = out.image_off, *voff = out.vimage_off;
   if (!ioff) {
-    XCHK(off_i.alloc(n1 * sizeof(long long)));
-    ioff = off_i.as<long long>();
+    XCHK(off_i.alloc(n1));
+    ioff = off_i.p;
   }
   if (!voff) {
-    XCHK(off_v.alloc(n1 * sizeof(long long)));
-    voff = off_v.as<long long>();
+    XCHK(off_v.alloc(n1));
+    voff = off_v.p;
   }
   size_t tb_scan = 0;
   const int* src = nullptr;
-  XCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_scan, c64_i.as<long long>(), ioff, (int)n1, st));
+  XCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_scan, c64_i.p, ioff, (int)n1, st));
   XCHK(temp.alloc(tb_scan));
   if (writer_order) {
     int* sorted = out.source;
     if (!sorted) {
-      XCHK(idx2.alloc(n * sizeof(int)));
-      sorted = idx2.as<int>();
+      XCHK(idx2.alloc(n));
+      sorted = idx2.p;
     }
-    XCHK(export_order(s, P, n, max_gwidth, sorted, cnt_i.as<int>(), cnt_v.as<int>(), st));
+    XCHK(export_order(s, P, n, max_gwidth, sorted, cnt_i.p, cnt_v.p, st));
     src = sorted;
   } else {  // model order: the counts only
     hipLaunchKernelGGL(export_key_kernel, dim3(grid_for(n, 256 / kKeyLanes)), dim3(256), 0, st, s, P, n, 0, 0LL,
-                       (unsigned long long*)nullptr, cnt_i.as<int>(), cnt_v.as<int>());
+                       (unsigned long long*)nullptr, cnt_i.p, cnt_v.p);
     XCHK(hipGetLastError());
     if (out.source) {
       hipLaunchKernelGGL(export_iota_kernel, dim3(grid_for(n, 256)), dim3(256), 0, st, out.source, n);
       XCHK(hipGetLastError());
     }
   }
-  hipLaunchKernelGGL(export_counts_kernel, dim3(grid_for((long long)n1, 256)), dim3(256), 0, st, src, cnt_i.as<int>(),
-                     cnt_v.as<int>(), n, c64_i.as<long long>(), c64_v.as<long long>());
+  hipLaunchKernelGGL(export_counts_kernel, dim3(grid_for((long long)n1, 256)), dim3(256), 0, st, src, cnt_i.p, cnt_v.p, n,
+                     c64_i.p, c64_v.p);
   XCHK(hipGetLastError());
-  XCHK(hipcub::DeviceScan::ExclusiveSum(temp.p, tb_scan, c64_i.as<long long>(), ioff, (int)n1, st));
-  XCHK(hipcub::DeviceScan::ExclusiveSum(temp.p, tb_scan, c64_v.as<long long>(), voff, (int)n1, st));
+  XCHK(hipcub::DeviceScan::ExclusiveSum(temp.p, tb_scan, c64_i.p, ioff, (int)n1, st));
+  XCHK(hipcub::DeviceScan::ExclusiveSum(temp.p, tb_scan, c64_v.p, voff, (int)n1, st));
   if (out.fields || out.colors || out.image_ids || out.image_idx || out.vimage_ids) {
     hipLaunchKernelGGL(export_gather_kernel, dim3(grid_for(n, 4)), dim3(256), 0, st, s, P, n, src, d_tab, ioff, voff,
                        out.fields, out.colors, out.image_ids, out.image_idx, out.vimage_ids);

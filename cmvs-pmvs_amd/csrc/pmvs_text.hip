@@ -222,22 +222,15 @@ inline int text_grid(long long items, int per_block) {
   return (int)(g < 1 ? 1 : (g > (1 << 16) ? (1 << 16) : g));
 }
 
-struct TextMem {  // device scratch of one call
-  void* p = nullptr;
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-  ~TextMem() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 }  // namespace
 
 hipError_t text_offsets(int kind, const TextArrays& in, int n, long long header_bytes, long long* d_off, hipStream_t st) {
   const int n1 = n + 1;
-  TextMem len, temp;
+  DevBuf<long long> len;
+  DevBuf<char> temp;
   size_t tb = 0;
-  TCHK(len.alloc((size_t)n1 * sizeof(long long)));
-  long long* d_len = static_cast<long long*>(len.p);
+  TCHK(len.alloc((size_t)n1));
+  long long* const d_len = len.p;
   TCHK(hipcub::DeviceScan::ExclusiveScan(nullptr, tb, d_len, d_off, hipcub::Sum(), header_bytes, n1, st));
   TCHK(temp.alloc(tb));
   if (kind == PMVS_TEXT_PLY)

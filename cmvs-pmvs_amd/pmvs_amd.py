@@ -615,20 +615,33 @@ class Scene:
         _check(self.lib.pmvs_loop_hash(self.handle, C.byref(h)))
         return int(h.value)
 
-    # pmvs_export_buffers: array name -> (dtype, shape from (patches, image entries, vimage entries))
-    EXPORT_ARRAYS = {"fields": ("float32", lambda n, e, v: (n, 11)), "colors": ("int32", lambda n, e, v: (n, 3)),
-                     "image_off": ("int64", lambda n, e, v: (n + 1,)), "image_ids": ("int32", lambda n, e, v: (e,)),
-                     "image_idx": ("int32", lambda n, e, v: (e,)), "vimage_off": ("int64", lambda n, e, v: (n + 1,)),
-                     "vimage_ids": ("int32", lambda n, e, v: (v,)), "source": ("int32", lambda n, e, v: (n,))}
+    # The arrays of the model-output calls, keyed and ordered as the fields of the C struct that points at
+    # them: name -> (dtype, shape); a name in a shape is a size the call supplies to _new_arrays.
+    # pmvs_export_buffers: n patches (n1 = n + 1), e image entries, v vimage entries
+    EXPORT_ARRAYS = {"fields": ("float32", ("n", 11)), "colors": ("int32", ("n", 3)), "image_off": ("int64", ("n1",)),
+                     "image_ids": ("int32", ("e",)), "image_idx": ("int32", ("e",)), "vimage_off": ("int64", ("n1",)),
+                     "vimage_ids": ("int32", ("v",)), "source": ("int32", ("n",))}
+    # pmvs_depthmap_buffers: c cells (depth maps) or pixels (pixel maps)
+    DEPTH_MAP_ARRAYS = {"patch": ("int32", ("c",)), "depth": ("float32", ("c",)), "normal": ("float32", ("c", 3)),
+                        "ncc": ("float32", ("c",))}
+    # pmvs_fuse_buffers: px pixels of the range, n points
+    FUSE_ARRAYS = {"support_map": ("uint8", ("px",)), "coord": ("float32", ("n", 3)), "normal": ("float32", ("n", 3)),
+                   "color": ("uint8", ("n", 3)), "support": ("uint8", ("n",)), "pixel": ("int64", ("n",)),
+                   "patch": ("int32", ("n",))}
+    # pmvs_tsdf_buffers: the volume's nx x ny x nz voxels; pmvs_mesh_buffers: v vertices, f faces
+    TSDF_ARRAYS = {"tsdf": ("float32", ("nz", "ny", "nx")), "obs": ("uint8", ("nz", "ny", "nx")),
+                   "color": ("uint8", ("nz", "ny", "nx", 4))}
+    MESH_ARRAYS = {"vertex": ("float32", ("v", 3)), "normal": ("float32", ("v", 3)), "color": ("uint8", ("v", 3)),
+                   "face": ("int32", ("f", 3))}
 
-    def _export_buffers(self, sizes: ExportSizes, device: bool, arrays):
-        """The arrays of one export (numpy, or torch tensors on the scene's device) and the
-        pmvs_export_buffers that points at them; names not in `arrays` stay NULL."""
-        names = list(self.EXPORT_ARRAYS) if arrays is None else list(arrays)
-        out, buf = {}, ExportBuffers()
-        for k in names:
-            dt, shape = self.EXPORT_ARRAYS[k]
-            shape = shape(sizes.patches, sizes.image_entries, sizes.vimage_entries)
+    def _new_arrays(self, Buffers, spec, names, device, **sizes):
+        """The arrays `names` (None = all) of `spec` (one of the tables above) as numpy arrays or torch
+        tensors on the scene's device, and the C struct that points at them (an empty array, and every
+        name not asked for, as NULL)."""
+        out, buf = {}, Buffers()
+        for k in (spec if names is None else names):
+            dt, shape = spec[k]
+            shape = tuple(sizes[d] if isinstance(d, str) else d for d in shape)
             if device:
                 import torch
                 out[k] = torch.empty(shape, dtype=getattr(torch, dt), device=torch.device("cuda", self.device))
@@ -639,14 +652,37 @@ class Scene:
         return out, buf
 
     @staticmethod
+    def _flags(writer_order: bool, device: bool) -> int:
+        return (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
+
+    @staticmethod
+    def _records(patches) -> np.ndarray:
+        return np.ascontiguousarray(patches, PATCH_DTYPE)
+
+    @staticmethod
     def _index2image(index2image):
         return None if index2image is None else np.ascontiguousarray(index2image, np.int32)
+
+    def _range(self, first_target, num_targets, radius=None):
+        """(num_targets, radius) with their defaults: all targets from first_target on, csize."""
+        return (self.desc.num_targets - first_target if num_targets is None else num_targets,
+                self.desc.csize if radius is None else radius)
 
     def loop_export_sizes(self) -> dict:
         """pmvs_loop_export_sizes: patches and list entries of the loop result on the device."""
         sz = ExportSizes()
         _check(self.lib.pmvs_loop_export_sizes(self.handle, C.byref(sz)))
         return {"patches": sz.patches, "image_entries": sz.image_entries, "vimage_entries": sz.vimage_entries}
+
+    def _export_call(self, sizes_call, call, writer_order, index2image, device, arrays):
+        """sizes_call(byref(sizes)), the arrays they ask for, then call(flags, index2image, byref(buffers))."""
+        sz = ExportSizes()
+        _check(sizes_call(C.byref(sz)))
+        out, buf = self._new_arrays(ExportBuffers, self.EXPORT_ARRAYS, arrays, device, n=sz.patches, n1=sz.patches + 1,
+                                    e=sz.image_entries, v=sz.vimage_entries)
+        tab = self._index2image(index2image)
+        _check(call(self._flags(writer_order, device), _ptr(tab), C.byref(buf)))
+        return out
 
     def loop_export(self, writer_order: bool = True, index2image=None, device: bool = False, arrays=None) -> dict:
         """pmvs_loop_export: the last run_loop(fetch=False) result as compact arrays, keyed by the
@@ -656,29 +692,16 @@ class Scene:
         of every view (None = the view indexes).  device=True: torch tensors allocated on the scene's
         device and written there (no host copy; import torch before the first Scene when torch ships
         its own HIP runtime, as bench.py does).  arrays: the names wanted (None = all)."""
-        sz = ExportSizes()
-        _check(self.lib.pmvs_loop_export_sizes(self.handle, C.byref(sz)))
-        out, buf = self._export_buffers(sz, device, arrays)
-        tab = self._index2image(index2image)
-        flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
-        _check(self.lib.pmvs_loop_export(self.handle, flags, _ptr(tab), C.byref(buf)))
-        return out
+        return self._export_call(lambda *a: self.lib.pmvs_loop_export_sizes(self.handle, *a),
+                                 lambda *a: self.lib.pmvs_loop_export(self.handle, *a), writer_order, index2image, device, arrays)
 
     def export_patches(self, patches: np.ndarray, writer_order: bool = True, index2image=None, device: bool = False,
                        arrays=None) -> dict:
         """pmvs_export_patches: loop_export's arrays for caller-supplied PATCH_DTYPE records."""
-        pa = np.ascontiguousarray(patches, PATCH_DTYPE)
-        sz = ExportSizes()
-        _check(self.lib.pmvs_export_patches_sizes(self.handle, _ptr(pa), len(pa), C.byref(sz)))
-        out, buf = self._export_buffers(sz, device, arrays)
-        tab = self._index2image(index2image)
-        flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
-        _check(self.lib.pmvs_export_patches(self.handle, _ptr(pa), len(pa), flags, _ptr(tab), C.byref(buf)))
-        return out
-
-    # pmvs_depthmap_buffers: array name -> (dtype, shape from the number of cells)
-    DEPTH_MAP_ARRAYS = {"patch": ("int32", lambda c: (c,)), "depth": ("float32", lambda c: (c,)),
-                        "normal": ("float32", lambda c: (c, 3)), "ncc": ("float32", lambda c: (c,))}
+        pa = self._records(patches)
+        return self._export_call(lambda *a: self.lib.pmvs_export_patches_sizes(self.handle, _ptr(pa), len(pa), *a),
+                                 lambda *a: self.lib.pmvs_export_patches(self.handle, _ptr(pa), len(pa), *a), writer_order,
+                                 index2image, device, arrays)
 
     def depth_map_layout(self):
         """pmvs_depth_map_layout: (dims [T, 2] int32 = every target's (gwidth, gheight), offsets [T + 1]
@@ -688,23 +711,10 @@ class Scene:
         _check(self.lib.pmvs_depth_map_layout(self.handle, _ptr(dims), _ptr(off)))
         return dims, off
 
-    def _depth_map_buffers(self, device: bool, arrays, cells=None):
-        """The arrays of one depth-map call (or, with `cells` pixels, of one pixel-map call) and the
-        pmvs_depthmap_buffers that points at them, by _export_buffers' conventions."""
-        if cells is None:
-            cells = int(self.depth_map_layout()[1][-1])
-        names = list(self.DEPTH_MAP_ARRAYS) if arrays is None else list(arrays)
-        out, buf = {}, DepthMapBuffers()
-        for k in names:
-            dt, shape = self.DEPTH_MAP_ARRAYS[k]
-            if device:
-                import torch
-                out[k] = torch.empty(shape(cells), dtype=getattr(torch, dt), device=torch.device("cuda", self.device))
-                setattr(buf, k, out[k].data_ptr() if out[k].numel() else None)
-            else:
-                out[k] = np.empty(shape(cells), dt)
-                setattr(buf, k, out[k].ctypes.data if out[k].size else None)
-        return out, buf
+    def _depth_map_call(self, call, writer_order, device, arrays):
+        out, buf = self._new_arrays(DepthMapBuffers, self.DEPTH_MAP_ARRAYS, arrays, device, c=int(self.depth_map_layout()[1][-1]))
+        _check(call(self._flags(writer_order, device), C.byref(buf)))
+        return out
 
     def loop_depth_maps(self, writer_order: bool = True, device: bool = False, arrays=None) -> dict:
         """pmvs_loop_depth_maps: what every target image sees of the last run_loop(fetch=False) result
@@ -714,36 +724,30 @@ class Scene:
         loop_export(writer_order=...) (model order: the records of loop_fetch).  Does not consume the
         result.  device=True: torch tensors on the scene's device, written there.  arrays: the names
         wanted (None = all)."""
-        out, buf = self._depth_map_buffers(device, arrays)
-        flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
-        _check(self.lib.pmvs_loop_depth_maps(self.handle, flags, C.byref(buf)))
-        return out
+        return self._depth_map_call(lambda *a: self.lib.pmvs_loop_depth_maps(self.handle, *a), writer_order, device, arrays)
 
     def depth_maps_patches(self, patches: np.ndarray, writer_order: bool = True, device: bool = False,
                            arrays=None) -> dict:
         """pmvs_depth_maps_patches: loop_depth_maps' arrays for caller-supplied PATCH_DTYPE records."""
-        pa = np.ascontiguousarray(patches, PATCH_DTYPE)
-        out, buf = self._depth_map_buffers(device, arrays)
-        flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
-        _check(self.lib.pmvs_depth_maps_patches(self.handle, _ptr(pa), len(pa), flags, C.byref(buf)))
-        return out
+        pa = self._records(patches)
+        return self._depth_map_call(lambda *a: self.lib.pmvs_depth_maps_patches(self.handle, _ptr(pa), len(pa), *a),
+                                    writer_order, device, arrays)
 
     def pixel_map_layout(self, first_target: int = 0, num_targets=None):
         """pmvs_pixel_map_layout: (dims [n, 2] int32 = the (width, height) of targets [first_target,
         first_target + num_targets) at the scene's level, offsets [n + 1] int64 = the first pixel of each
         target's map relative to the first, the last entry the total).  num_targets None: all from
         first_target on."""
-        num = self.desc.num_targets - first_target if num_targets is None else num_targets
+        num, _ = self._range(first_target, num_targets)
         dims, off = np.zeros((max(num, 0), 2), np.int32), np.zeros(max(num, 0) + 1, np.int64)
         _check(self.lib.pmvs_pixel_map_layout(self.handle, first_target, num, _ptr(dims), _ptr(off)))
         return dims, off
 
     def _pixel_map_call(self, call, writer_order, device, arrays, first_target, num_targets, radius):
-        num = self.desc.num_targets - first_target if num_targets is None else num_targets
-        radius = self.desc.csize if radius is None else radius
-        out, buf = self._depth_map_buffers(device, arrays, int(self.pixel_map_layout(first_target, num)[1][-1]))
-        flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
-        _check(call(flags, first_target, num, radius, C.byref(buf)))
+        num, radius = self._range(first_target, num_targets, radius)
+        out, buf = self._new_arrays(DepthMapBuffers, self.DEPTH_MAP_ARRAYS, arrays, device,
+                                    c=int(self.pixel_map_layout(first_target, num)[1][-1]))
+        _check(call(self._flags(writer_order, device), first_target, num, radius, C.byref(buf)))
         return out
 
     def loop_pixel_maps(self, writer_order: bool = True, device: bool = False, arrays=None, first_target: int = 0,
@@ -761,35 +765,20 @@ class Scene:
     def pixel_maps_patches(self, patches: np.ndarray, writer_order: bool = True, device: bool = False, arrays=None,
                            first_target: int = 0, num_targets=None, radius=None) -> dict:
         """pmvs_pixel_maps_patches: loop_pixel_maps' arrays for caller-supplied PATCH_DTYPE records."""
-        pa = np.ascontiguousarray(patches, PATCH_DTYPE)
+        pa = self._records(patches)
         return self._pixel_map_call(lambda *a: self.lib.pmvs_pixel_maps_patches(self.handle, _ptr(pa), len(pa), *a),
                                     writer_order, device, arrays, first_target, num_targets, radius)
 
-    # pmvs_fuse_buffers: array name -> (dtype, shape from (pixels of the range, points))
-    FUSE_ARRAYS = {"support_map": ("uint8", lambda px, n: (px,)), "coord": ("float32", lambda px, n: (n, 3)),
-                   "normal": ("float32", lambda px, n: (n, 3)), "color": ("uint8", lambda px, n: (n, 3)),
-                   "support": ("uint8", lambda px, n: (n,)), "pixel": ("int64", lambda px, n: (n,)),
-                   "patch": ("int32", lambda px, n: (n,))}
-
     def _fuse_call(self, call, writer_order, device, arrays, first_target, num_targets, radius, min_support, depth_rel,
                    normal_cos):
-        num = self.desc.num_targets - first_target if num_targets is None else num_targets
-        prm = FuseParams(self.desc.csize if radius is None else radius, min_support, depth_rel, normal_cos)
-        flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
+        num, radius = self._range(first_target, num_targets, radius)
+        prm = FuseParams(radius, min_support, depth_rel, normal_cos)
+        flags = self._flags(writer_order, device)
         count = C.c_int64(0)
         _check(call(flags, first_target, num, C.byref(prm), 0, C.byref(FuseBuffers()), C.byref(count)))  # the counting call
-        pixels, n = int(self.pixel_map_layout(first_target, num)[1][-1]), int(count.value)
-        names = list(self.FUSE_ARRAYS) if arrays is None else list(arrays)
-        out, buf = {}, FuseBuffers()
-        for k in names:
-            dt, shape = self.FUSE_ARRAYS[k]
-            if device:
-                import torch
-                out[k] = torch.empty(shape(pixels, n), dtype=getattr(torch, dt), device=torch.device("cuda", self.device))
-                setattr(buf, k, out[k].data_ptr() if out[k].numel() else None)
-            else:
-                out[k] = np.empty(shape(pixels, n), dt)
-                setattr(buf, k, out[k].ctypes.data if out[k].size else None)
+        n = int(count.value)
+        out, buf = self._new_arrays(FuseBuffers, self.FUSE_ARRAYS, arrays, device,
+                                    px=int(self.pixel_map_layout(first_target, num)[1][-1]), n=n)
         _check(call(flags, first_target, num, C.byref(prm), n, C.byref(buf), C.byref(count)))
         if int(count.value) != n:
             raise PmvsError(f"the fusion emitted {count.value} points after counting {n}")
@@ -813,41 +802,20 @@ class Scene:
                      first_target: int = 0, num_targets=None, radius=None, min_support: int = 2, depth_rel: float = 0.01,
                      normal_cos: float = 0.5) -> dict:
         """pmvs_fuse_patches: loop_fuse's arrays for caller-supplied PATCH_DTYPE records."""
-        pa = np.ascontiguousarray(patches, PATCH_DTYPE)
+        pa = self._records(patches)
         return self._fuse_call(lambda *a: self.lib.pmvs_fuse_patches(self.handle, _ptr(pa), len(pa), *a), writer_order,
                                device, arrays, first_target, num_targets, radius, min_support, depth_rel, normal_cos)
-
-    # pmvs_tsdf_buffers / pmvs_mesh_buffers: array name -> (dtype, trailing shape)
-    TSDF_ARRAYS = {"tsdf": ("float32", ()), "obs": ("uint8", ()), "color": ("uint8", (4,))}
-    MESH_ARRAYS = {"vertex": ("float32", "v"), "normal": ("float32", "v"), "color": ("uint8", "v"), "face": ("int32", "f")}
-
-    def _new_arrays(self, Buffers, spec, names, device):
-        """The arrays `names` of `spec` (name -> (dtype, shape)) as numpy arrays or torch tensors on the
-        scene's device, and the C struct that points at them (an empty array as NULL)."""
-        out, buf = {}, Buffers()
-        for k in names:
-            dt, shape = spec[k]
-            if device:
-                import torch
-                out[k] = torch.empty(shape, dtype=getattr(torch, dt), device=torch.device("cuda", self.device))
-                setattr(buf, k, out[k].data_ptr() if out[k].numel() else None)
-            else:
-                out[k] = np.empty(shape, dt)
-                setattr(buf, k, out[k].ctypes.data if out[k].size else None)
-        return out, buf
 
     def _tsdf_params(self, volume, trunc, writer_order, device, first_target, num_targets, radius, min_support, depth_rel,
                      normal_cos):
         """(flags, first, num, byref(params), byref(volume)): the arguments the TSDF and mesh calls share."""
-        num = self.desc.num_targets - first_target if num_targets is None else num_targets
-        prm = TsdfParams(FuseParams(self.desc.csize if radius is None else radius, min_support, depth_rel, normal_cos), trunc)
-        flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
-        return flags, first_target, num, C.byref(prm), C.byref(volume)
+        num, radius = self._range(first_target, num_targets, radius)
+        prm = TsdfParams(FuseParams(radius, min_support, depth_rel, normal_cos), trunc)
+        return self._flags(writer_order, device), first_target, num, C.byref(prm), C.byref(volume)
 
     def _tsdf_call(self, call, volume, device, arrays, shared):
         nx, ny, nz = volume.dims
-        spec = {k: (dt, (nz, ny, nx) + tail) for k, (dt, tail) in self.TSDF_ARRAYS.items()}
-        out, buf = self._new_arrays(TsdfBuffers, spec, list(spec) if arrays is None else list(arrays), device)
+        out, buf = self._new_arrays(TsdfBuffers, self.TSDF_ARRAYS, arrays, device, nx=nx, ny=ny, nz=nz)
         _check(call(*shared, C.byref(buf)))
         return out
 
@@ -868,7 +836,7 @@ class Scene:
                      arrays=None, first_target: int = 0, num_targets=None, radius=None, min_support: int = 2,
                      depth_rel: float = 0.01, normal_cos: float = 0.5) -> dict:
         """pmvs_tsdf_patches: loop_tsdf's arrays for caller-supplied PATCH_DTYPE records."""
-        pa = np.ascontiguousarray(patches, PATCH_DTYPE)
+        pa = self._records(patches)
         shared = self._tsdf_params(volume, trunc, writer_order, device, first_target, num_targets, radius, min_support,
                                    depth_rel, normal_cos)
         return self._tsdf_call(lambda *a: self.lib.pmvs_tsdf_patches(self.handle, _ptr(pa), len(pa), *a), volume, device,
@@ -879,8 +847,7 @@ class Scene:
         nv, nf = C.c_int64(0), C.c_int64(0)
         _check(call(0, 0, C.byref(MeshBuffers()), C.byref(nv), C.byref(nf)))
         v, f = int(nv.value), int(nf.value)
-        spec = {k: (dt, (v if n == "v" else f, 3)) for k, (dt, n) in self.MESH_ARRAYS.items()}
-        out, buf = self._new_arrays(MeshBuffers, spec, list(spec) if arrays is None else list(arrays), device)
+        out, buf = self._new_arrays(MeshBuffers, self.MESH_ARRAYS, arrays, device, v=v, f=f)
         _check(call(v, f, C.byref(buf), C.byref(nv), C.byref(nf)))
         if (int(nv.value), int(nf.value)) != (v, f):
             raise PmvsError(f"the mesh has {nv.value} vertices and {nf.value} faces after counting {v} and {f}")
@@ -905,7 +872,7 @@ class Scene:
             sizes, ptrs = [0 if a is None else a.size for a in ins], [_ptr(a) for a in ins]
         if sizes[:2] != [voxels, voxels] or sizes[2] not in (0, 4 * voxels):
             raise ValueError("tsdf_mesh: the arrays do not have the volume's size")
-        flags = EXPORT_DEVICE if device else 0
+        flags = self._flags(False, device)
         return self._mesh_call(lambda *a: self.lib.pmvs_tsdf_mesh(self.handle, flags, C.byref(volume), min_obs, *ptrs, *a),
                                device, arrays)
 
@@ -922,17 +889,20 @@ class Scene:
                      device: bool = False, arrays=None, first_target: int = 0, num_targets=None, radius=None,
                      min_support: int = 2, depth_rel: float = 0.01, normal_cos: float = 0.5) -> dict:
         """pmvs_mesh_patches: loop_mesh's arrays for caller-supplied PATCH_DTYPE records."""
-        pa = np.ascontiguousarray(patches, PATCH_DTYPE)
+        pa = self._records(patches)
         shared = self._tsdf_params(volume, trunc, writer_order, device, first_target, num_targets, radius, min_support,
                                    depth_rel, normal_cos)
         return self._mesh_call(lambda *a: self.lib.pmvs_mesh_patches(self.handle, _ptr(pa), len(pa), *shared, min_obs, *a),
                                device, arrays)
 
-    def _text(self, call, device: bool, out):
-        """A size query, the buffer (numpy uint8, or a torch uint8 tensor on the scene's device; `out`
-        supplies it) and the call that fills it; returns the buffer cut to the text's size."""
+    def _text(self, call, writer_order, index2image, device: bool, out):
+        """call(flags, index2image, out, cap, byref(size)): a size query, the buffer (numpy uint8, or a torch
+        uint8 tensor on the scene's device; `out` supplies it) and the call that fills it; returns the
+        buffer cut to the text's size."""
+        tab = self._index2image(index2image)
+        head = (self._flags(writer_order, device), _ptr(tab))
         size = C.c_int64(0)
-        _check(call(None, 0, C.byref(size)))
+        _check(call(*head, None, 0, C.byref(size)))
         n = int(size.value)
         if device:
             import torch
@@ -946,7 +916,7 @@ class Scene:
         if n > cap:
             raise PmvsError(f"the text has {n} bytes, `out` holds {cap}")
         if n:
-            _check(call(ptr, cap, C.byref(size)))
+            _check(call(*head, ptr, cap, C.byref(size)))
         return out[:n]
 
     def loop_text(self, kind: int, writer_order: bool = True, index2image=None, device: bool = False, out=None):
@@ -955,19 +925,14 @@ class Scene:
         write_patches / write_pset write from loop_export of the same flags, as a numpy uint8 array
         (device=True: a torch uint8 tensor on the scene's device, nothing crosses PCIe).  Does not
         consume the result.  out: a uint8 buffer of at least the text's size to use."""
-        tab = self._index2image(index2image)
-        flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
-        return self._text(lambda ptr, cap, size: self.lib.pmvs_loop_text(self.handle, kind, flags, _ptr(tab), ptr, cap, size),
-                          device, out)
+        return self._text(lambda *a: self.lib.pmvs_loop_text(self.handle, kind, *a), writer_order, index2image, device, out)
 
     def text_patches(self, patches: np.ndarray, kind: int, writer_order: bool = True, index2image=None,
                      device: bool = False, out=None):
         """pmvs_text_patches: loop_text's bytes for caller-supplied PATCH_DTYPE records."""
-        pa = np.ascontiguousarray(patches, PATCH_DTYPE)
-        tab = self._index2image(index2image)
-        flags = (EXPORT_WRITER_ORDER if writer_order else 0) | (EXPORT_DEVICE if device else 0)
-        return self._text(lambda ptr, cap, size: self.lib.pmvs_text_patches(self.handle, _ptr(pa), len(pa), kind, flags,
-                                                                            _ptr(tab), ptr, cap, size), device, out)
+        pa = self._records(patches)
+        return self._text(lambda *a: self.lib.pmvs_text_patches(self.handle, _ptr(pa), len(pa), kind, *a), writer_order,
+                          index2image, device, out)
 
     def patch_colors(self, coords: np.ndarray, images) -> np.ndarray:
         """writePLY colour mode 0 for patches (coords [n,4], images: list of view-index lists)."""

@@ -1,4 +1,4 @@
-// Host stub of the few HIP calls cmvs-pmvs_amd/csrc/pmvs_devbuf.h makes (tests/csrc/devbuf_test.cpp):
+// Host stub of the few HIP calls cmvs-pmvs_amd/csrc/pmvs_devbuf.h makes (tests/csrc/devbuf_test.cpp, staging_test.cpp):
 // device memory is malloc'ed host memory, every live allocation is recorded, freeing an address that
 // is not live (a double free) is counted, and the next allocation can be made to fail.
 #pragma once

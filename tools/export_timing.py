@@ -79,7 +79,8 @@ def main():
         sz = P.ExportSizes()
         P._check(lib.pmvs_loop_export_sizes(scene.handle, C.byref(sz)))
         t1 = time.perf_counter()
-        out, buf = scene._export_buffers(sz, False, names)
+        out, buf = scene._new_arrays(P.ExportBuffers, scene.EXPORT_ARRAYS, names, False, n=sz.patches, n1=sz.patches + 1,
+                                     e=sz.image_entries, v=sz.vimage_entries)
         P._check(lib.pmvs_loop_export(scene.handle, P.EXPORT_WRITER_ORDER, P._ptr(index2image), C.byref(buf)))
         t2 = time.perf_counter()
         e, ve = int(sz.image_entries), int(sz.vimage_entries)

@@ -63,7 +63,6 @@ def main():
         e1.synchronize()
         return out, e0.elapsed_time(e1), (time.perf_counter() - t0) * 1e3
 
-    dev = torch.device("cuda", scene.device)
     flags = P.EXPORT_WRITER_ORDER | P.EXPORT_DEVICE
     prm = P.FuseParams(inp.csize, 2, 0.01, 0.5)
     ranges = {"all_targets": (0, tnum), "one_target": (mid, 1)}
@@ -77,14 +76,11 @@ def main():
             P._check(scene.lib.pmvs_loop_fuse(scene.handle, flags, first, num, C.byref(prm), 0, C.byref(P.FuseBuffers()),
                                               C.byref(cnt)))
             counts[name] = int(cnt.value)
-            bufs[name] = {k: torch.empty(shape(pixels, counts[name]), dtype=getattr(torch, dt), device=dev)
-                          for k, (dt, shape) in P.Scene.FUSE_ARRAYS.items()}
-        b = P.FuseBuffers()
-        for k, t in bufs[name].items():
-            setattr(b, k, t.data_ptr() if t.numel() else None)
+            bufs[name] = scene._new_arrays(P.FuseBuffers, scene.FUSE_ARRAYS, None, True, px=pixels, n=counts[name])
+        out, b = bufs[name]
         P._check(scene.lib.pmvs_loop_fuse(scene.handle, flags, first, num, C.byref(prm), counts[name], C.byref(b), C.byref(cnt)))
         assert int(cnt.value) == counts[name]
-        return bufs[name]
+        return out
 
     calls = {"fuse_one_target": lambda: fuse("one_target"),
              "pixel_maps_one_target": lambda: scene.loop_pixel_maps(writer_order=True, device=True, first_target=mid, num_targets=1),
