@@ -1,4 +1,4 @@
-// pmvs2_main.cpp -- the `pmvs2 prefix option_file [PATCH] [PSET] [DEPTH] [PIXDEPTH] [FUSE] [MESH]` executable (reference
+// pmvs2_main.cpp -- the `pmvs2 prefix option_file [PATCH] [PSET] [DEPTH] [PIXDEPTH] [FUSE] [MESH] [FINEMESH]` executable (reference
 // source/pmvs.cpp:7-63 with CFindMatch::init / run / write, findMatch.cpp:30-224), driving the
 // MI355X-native core through its C-ABI (include/pmvs_amd.h).  A drop-in for the program
 // genOption's pmvs.sh calls (genOption.cpp:73): same arguments, same input tree
@@ -126,7 +126,7 @@ void usage(const char* argv0) {
             << "oimages  5  0 2 4 6 8 (enumeration)" << std::endl
             << "        -1  24 48 (range specification)" << std::endl
             << std::endl
-            << "[Optional export] PATCH PSET DEPTH PIXDEPTH FUSE MESH" << std::endl
+            << "[Optional export] PATCH PSET DEPTH PIXDEPTH FUSE MESH FINEMESH" << std::endl
             << " i.e export patch and pset: prefix option_file PATCH PSET"
             << " i.e export patch only: prefix option_file PATCH" << std::endl
             << " DEPTH: every target image's depth map, one value per csize x csize cell, as" << std::endl
@@ -141,7 +141,11 @@ void usage(const char* argv0) {
             << "        binary PLY models/option_file.fused.ply (x y z nx ny nz, colour, support)" << std::endl
             << " MESH: FUSE's maps integrated into a truncated signed distance volume (the fused cloud's bounding" << std::endl
             << "        box padded by 3 voxels, voxel = its longest extent / 256, truncation 3 voxels) and meshed by" << std::endl
-            << "        naive surface nets, as the binary PLY models/option_file.mesh.ply (x y z nx ny nz, colour; faces)" << std::endl;
+            << "        naive surface nets, as the binary PLY models/option_file.mesh.ply (x y z nx ny nz, colour; faces)" << std::endl
+            << " FINEMESH: the same mesh at image resolution, in a sparse volume of 8x8x8-voxel bricks that exists only" << std::endl
+            << "        within 5 voxels of the fused points: voxel = the cloud's longest extent / min(4096, the largest" << std::endl
+            << "        width or height of the target images at the level), truncation 3 voxels, as the binary PLY" << std::endl
+            << "        models/option_file.finemesh.ply" << std::endl;
 }
 
 }  // namespace
@@ -154,7 +158,8 @@ int main(int argc, char* argv[]) {
   for (int i = 0; i < argc; ++i) std::cout << std::endl << argv[i];
   std::cout << std::endl;
   const std::string prefix = argv[1], option = argv[2];
-  bool export_patch = false, export_pset = false, export_depth = false, export_pixdepth = false, export_fuse = false, export_mesh = false;
+  bool export_patch = false, export_pset = false, export_depth = false, export_pixdepth = false, export_fuse = false, export_mesh = false,
+       export_finemesh = false;
   for (int i = 3; i < argc; ++i) {
     if (std::string(argv[i]) == "PATCH") export_patch = true;
     if (std::string(argv[i]) == "PSET") export_pset = true;
@@ -162,6 +167,7 @@ int main(int argc, char* argv[]) {
     if (std::string(argv[i]) == "PIXDEPTH") export_pixdepth = true;
     if (std::string(argv[i]) == "FUSE") export_fuse = true;
     if (std::string(argv[i]) == "MESH") export_mesh = true;
+    if (std::string(argv[i]) == "FINEMESH") export_finemesh = true;
   }
   const double t0 = now_s();
 
@@ -462,7 +468,7 @@ int main(int argc, char* argv[]) {
       CHECK("pfm", pmvs_write_pfm((out + name).c_str(), dims[0], dims[1], depth.data()));
     }
   }
-  if (export_fuse || export_mesh) {
+  if (export_fuse || export_mesh || export_finemesh) {
     // the model just written fused over all target images (pmvs_loop_fuse, writer order): a counting
     // call sizes the host arrays
     pmvs_fuse_params fp{};
@@ -508,6 +514,33 @@ int main(int argc, char* argv[]) {
       }
       CHECK("mesh ply", pmvs_write_ply_mesh_binary((out + ".mesh.ply").c_str(), nv, vertex.data(), vnormal.data(),
                                                    vcolor.data(), nf, face.data()));
+    }
+    if (export_finemesh) {
+      // the same maps meshed in a sparse brick volume (pmvs_loop_brick_mesh) whose voxel follows the target
+      // images' resolution; a cloud with no extent gives an empty mesh
+      int64_t nv = 0, nf = 0;
+      std::vector<float> vertex, vnormal;
+      std::vector<uint8_t> vcolor;
+      std::vector<int32_t> face;
+      std::vector<int32_t> dims((size_t)tnum * 2);
+      CHECK("pixel maps", pmvs_pixel_map_layout(sc, 0, tnum, dims.data(), nullptr));
+      const int32_t cells = std::min<int32_t>(4096, *std::max_element(dims.begin(), dims.end()));
+      pmvs_volume vol{};
+      if (npts > 0 && pmvs_brick_volume_from_points(npts, coord.data(), cells, 3, &vol) == PMVS_OK) {
+        pmvs_brick_params bp{};
+        bp.tsdf.fuse = fp;
+        bp.tsdf.trunc = 3.0f * vol.voxel;
+        bp.margin = 5;  // ceil(trunc / voxel) + 2
+        pmvs_mesh_buffers mb{};
+        CHECK("fine mesh", pmvs_loop_brick_mesh(sc, PMVS_EXPORT_WRITER_ORDER, 0, tnum, &bp, &vol, 1, 0, 0, &mb, &nv, &nf));
+        vertex.resize((size_t)nv * 3), vnormal.resize((size_t)nv * 3), vcolor.resize((size_t)nv * 3), face.resize((size_t)nf * 3);
+        mb.vertex = vertex.data(), mb.normal = vnormal.data(), mb.color = vcolor.data(), mb.face = face.data();
+        int64_t wv = 0, wf = 0;
+        CHECK("fine mesh", pmvs_loop_brick_mesh(sc, PMVS_EXPORT_WRITER_ORDER, 0, tnum, &bp, &vol, 1, nv, nf, &mb, &wv, &wf));
+        nv = std::min(nv, wv), nf = std::min(nf, wf);
+      }
+      CHECK("fine mesh ply", pmvs_write_ply_mesh_binary((out + ".finemesh.ply").c_str(), nv, vertex.data(), vnormal.data(),
+                                                        vcolor.data(), nf, face.data()));
     }
   }
   pmvs_scene_destroy(sc);

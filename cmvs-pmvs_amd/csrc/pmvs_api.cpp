@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/pmvs_amd.h"
+#include "pmvs_brick.h"
 #include "pmvs_features.h"
 #include "pmvs_fmt.h"
 #include "pmvs_launch.h"
@@ -1930,6 +1931,203 @@ pmvs_status pmvs_mesh_patches(pmvs_scene* sc, const pmvs_patch* patches, int32_t
   const pmvs_patch* dP = nullptr;
   if (pmvs_status st = upload_records(sc, patches, n, nullptr, arena, &dP)) return st;
   return mesh_records(sc, dP, n, flags, first_target, num_targets, params, volume, min_obs, vcap, fcap, buffers, nverts, nfaces);
+}
+
+// ---- the sparse brick volume (pmvs_brick.hip)
+namespace {
+bool brick_volume_ok(const pmvs_volume* v) {
+  if (!v || !std::isfinite(v->origin[0]) || !std::isfinite(v->origin[1]) || !std::isfinite(v->origin[2])) return false;
+  if (!std::isfinite(v->voxel) || !(v->voxel > 0.0f)) return false;
+  for (int a = 0; a < 3; ++a)
+    if (v->dims[a] < 1 || v->dims[a] > PMVS_BRICK_MAX_DIM) return false;
+  return pmvsbrick::grid_of(v->dims).bricks() <= INT32_MAX;  // at most 2^51: no overflow
+}
+
+bool brick_args_ok(const pmvs_scene* sc, int32_t flags, int32_t first, int32_t num, const pmvs_brick_params* p,
+                   const pmvs_volume* v) {
+  return p && tsdf_params_ok(&p->tsdf) && p->margin >= 0 && p->margin <= PMVS_BRICK_MAX_MARGIN && brick_volume_ok(v) &&
+         range_call_ok(sc, flags, first, num);
+}
+
+enum { kBricks = 1 };  // Staging part: the brick arrays share the stored count
+
+// The bricks of the device records dP[0, n): selection, then the first min(count, bcap) integrated.
+pmvs_status brick_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, int32_t flags, int32_t first, int32_t num,
+                          const pmvs_brick_params* prm, const pmvs_volume* vol, int64_t bcap, const pmvs_brick_buffers* b,
+                          int64_t* nbricks) {
+  CallArena arena;
+  Staging stg(arena, (flags & PMVS_EXPORT_DEVICE) != 0);
+  FuseMaps f;
+  BrickSelection sel;
+  if (pmvs_status st = tsdf_maps(sc, dP, n, flags, first, num, prm->tsdf.fuse, arena, f)) return st;
+  EXPCHK(brick_select(sc->ds, f, first, num, *vol, prm->margin, sel, sc->stream));
+  *nbricks = sel.total;
+  const size_t stored = (size_t)std::min<int64_t>(bcap, sel.total);  // the staging is sized by what exists
+  long long* keys = nullptr;
+  TsdfArrays a;
+  EXPCHK(stg.capped(&keys, b->brick, stored, 1, kBricks));
+  EXPCHK(stg.capped(&a.tsdf, b->tsdf, stored, PMVS_BRICK * PMVS_BRICK * PMVS_BRICK, kBricks));
+  EXPCHK(stg.capped(&a.obs, b->obs, stored, PMVS_BRICK * PMVS_BRICK * PMVS_BRICK, kBricks));
+  EXPCHK(stg.capped(&a.color, b->color, stored, PMVS_BRICK * PMVS_BRICK * PMVS_BRICK * 4, kBricks));
+  if (stored > 0 && (keys || a.tsdf || a.obs || a.color)) {
+    if (!keys) EXPCHK(arena.alloc(&keys, stored));  // the integration reads the list, wanted or not
+    EXPCHK(brick_keys(sel, (long long)stored, keys, sc->stream));
+    EXPCHK(brick_integrate(sc->ds, f, first, num, *vol, prm->tsdf.trunc, keys, (long long)stored, a, sc->stream));
+  }
+  stg.wrote(kBricks, stored);
+  EXPCHK(stg.finish(sc->stream, true));  // in device mode too: the maps and the selection are freed on return
+  return PMVS_OK;
+}
+
+// Surface nets over device bricks into the caller's buffers (device mode) or through staging.
+pmvs_status brick_mesh_device(pmvs_scene* sc, bool dev, const pmvs_volume* vol, int32_t min_obs, int64_t nb, const long long* d_key,
+                              const int* d_slot, const float* d_tsdf, const uint8_t* d_obs, const uint8_t* d_color, int64_t vcap,
+                              int64_t fcap, const pmvs_mesh_buffers* b, int64_t* nverts, int64_t* nfaces) {
+  const int64_t voxels = nb * (PMVS_BRICK * PMVS_BRICK * PMVS_BRICK);  // stored: < 2^40
+  // no more vertices than stored voxels and no more faces than 6 per stored voxel exist
+  const size_t nv = (size_t)std::min<int64_t>(vcap, voxels), nf = (size_t)std::min<int64_t>(fcap, voxels * 6);
+  CallArena arena;
+  Staging stg(arena, dev);
+  MeshArrays a;
+  EXPCHK(stg.capped(&a.vertex, b->vertex, nv, 3, kVertices));
+  EXPCHK(stg.capped(&a.normal, b->normal, nv, 3, kVertices));
+  EXPCHK(stg.capped(&a.color, b->color, nv, 3, kVertices));
+  EXPCHK(stg.capped(&a.face, b->face, nf, 3, kFaces));
+  long long tv = 0, tf = 0;
+  EXPCHK(brick_mesh_pass(*vol, min_obs, nb, d_key, d_slot, d_tsdf, d_obs, d_color, (long long)nv, (long long)nf, a, &tv, &tf,
+                         sc->stream));
+  *nverts = tv;
+  *nfaces = tf;
+  if (tv > INT32_MAX) return fail(PMVS_EUNSUPPORTED, "brick mesh: %lld vertices do not fit the int32 face ids", tv);
+  stg.wrote(kVertices, (size_t)tv);
+  stg.wrote(kFaces, (size_t)tf);
+  EXPCHK(stg.finish(sc->stream));
+  return PMVS_OK;
+}
+
+// Selection, integration, then extraction of the device records dP[0, n): the bricks stay on the device.
+pmvs_status brick_mesh_records(pmvs_scene* sc, const pmvs_patch* dP, int32_t n, int32_t flags, int32_t first, int32_t num,
+                               const pmvs_brick_params* prm, const pmvs_volume* vol, int32_t min_obs, int64_t vcap, int64_t fcap,
+                               const pmvs_mesh_buffers* b, int64_t* nverts, int64_t* nfaces) {
+  CallArena arena;
+  BrickSelection sel;
+  long long* keys = nullptr;
+  TsdfArrays a;
+  {
+    FuseMaps f;
+    if (pmvs_status st = tsdf_maps(sc, dP, n, flags, first, num, prm->tsdf.fuse, arena, f)) return st;
+    EXPCHK(brick_select(sc->ds, f, first, num, *vol, prm->margin, sel, sc->stream));
+    const size_t voxels = (size_t)sel.total * (PMVS_BRICK * PMVS_BRICK * PMVS_BRICK);
+    EXPCHK(arena.alloc(&keys, (size_t)sel.total));
+    EXPCHK(arena.alloc(&a.tsdf, voxels));
+    EXPCHK(arena.alloc(&a.obs, voxels));
+    EXPCHK(arena.alloc(&a.color, voxels * 4));
+    EXPCHK(brick_keys(sel, sel.total, keys, sc->stream));
+    EXPCHK(brick_integrate(sc->ds, f, first, num, *vol, prm->tsdf.trunc, keys, sel.total, a, sc->stream));
+    EXPCHK(hipStreamSynchronize(sc->stream));  // the maps are freed here, before the extraction's scratch
+  }
+  sel.flag.release();
+  return brick_mesh_device(sc, (flags & PMVS_EXPORT_DEVICE) != 0, vol, min_obs, sel.total, keys, sel.slot.p, a.tsdf, a.obs, a.color,
+                           vcap, fcap, b, nverts, nfaces);
+}
+}  // namespace
+
+pmvs_status pmvs_loop_brick_tsdf(pmvs_scene* sc, int32_t flags, int32_t first_target, int32_t num_targets,
+                                 const pmvs_brick_params* params, const pmvs_volume* volume, int64_t bcap,
+                                 const pmvs_brick_buffers* buffers, int64_t* nbricks) {
+  if (!buffers || !nbricks || bcap < 0 || !brick_args_ok(sc, flags, first_target, num_targets, params, volume))
+    return fail(PMVS_EINVAL, "invalid argument");
+  const pmvs_patch* dP = nullptr;
+  int32_t n = 0;
+  if (pmvs_status st = loop_records(sc, "loop_brick_tsdf", &dP, &n)) return st;
+  return brick_records(sc, dP, n, flags, first_target, num_targets, params, volume, bcap, buffers, nbricks);
+}
+
+pmvs_status pmvs_brick_tsdf_patches(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, int32_t flags, int32_t first_target,
+                                    int32_t num_targets, const pmvs_brick_params* params, const pmvs_volume* volume, int64_t bcap,
+                                    const pmvs_brick_buffers* buffers, int64_t* nbricks) {
+  if (!buffers || !nbricks || bcap < 0 || !records_ok(patches, n) ||
+      !brick_args_ok(sc, flags, first_target, num_targets, params, volume))
+    return fail(PMVS_EINVAL, "invalid argument");
+  CallArena arena;
+  const pmvs_patch* dP = nullptr;
+  if (pmvs_status st = upload_records(sc, patches, n, nullptr, arena, &dP)) return st;
+  return brick_records(sc, dP, n, flags, first_target, num_targets, params, volume, bcap, buffers, nbricks);
+}
+
+pmvs_status pmvs_brick_tsdf_mesh(pmvs_scene* sc, int32_t flags, const pmvs_volume* volume, int32_t min_obs, int64_t nbricks,
+                                 const int64_t* brick, const float* tsdf, const uint8_t* obs, const uint8_t* color, int64_t vcap,
+                                 int64_t fcap, const pmvs_mesh_buffers* buffers, int64_t* nverts, int64_t* nfaces) {
+  if (!sc || !flags_ok(flags, PMVS_EXPORT_DEVICE) || !brick_volume_ok(volume) || nbricks < 0 ||
+      (nbricks > 0 && (!brick || !tsdf || !obs)) || !mesh_args_ok(min_obs, vcap, fcap, buffers, nverts, nfaces))
+    return fail(PMVS_EINVAL, "invalid argument");
+  const bool dev = (flags & PMVS_EXPORT_DEVICE) != 0;
+  const int64_t grid = pmvsbrick::grid_of(volume->dims).bricks();
+  if (nbricks > grid) return fail(PMVS_EINVAL, "brick_tsdf_mesh: more bricks than the grid holds");
+  if (!dev)  // host keys are checked here, before the scene is touched; device keys by a kernel below
+    for (int64_t s = 0; s < nbricks; ++s)
+      if (brick[s] < 0 || brick[s] >= grid || (s > 0 && brick[s - 1] >= brick[s]))
+        return fail(PMVS_EINVAL, "brick_tsdf_mesh: key %lld is outside the grid or not ascending", (long long)s);
+  *nverts = *nfaces = 0;
+  if (nbricks == 0) return PMVS_OK;  // an empty volume: an empty mesh
+  HIPCHK(hipSetDevice(sc->device));
+  CallArena arena;
+  const long long* d_key = reinterpret_cast<const long long*>(brick);
+  if (!dev) {  // the bricks go up
+    const size_t nb = (size_t)nbricks, voxels = nb * (PMVS_BRICK * PMVS_BRICK * PMVS_BRICK);
+    long long* u_key = nullptr;
+    float* d_tsdf = nullptr;
+    uint8_t *d_obs = nullptr, *d_color = nullptr;
+    EXPCHK(arena.alloc(&u_key, nb));
+    EXPCHK(arena.alloc(&d_tsdf, voxels));
+    EXPCHK(arena.alloc(&d_obs, voxels));
+    EXPCHK(hipMemcpyAsync(u_key, brick, nb * sizeof(int64_t), hipMemcpyHostToDevice, sc->stream));
+    EXPCHK(hipMemcpyAsync(d_tsdf, tsdf, voxels * sizeof(float), hipMemcpyHostToDevice, sc->stream));
+    EXPCHK(hipMemcpyAsync(d_obs, obs, voxels, hipMemcpyHostToDevice, sc->stream));
+    if (color) {
+      EXPCHK(arena.alloc(&d_color, voxels * 4));
+      EXPCHK(hipMemcpyAsync(d_color, color, voxels * 4, hipMemcpyHostToDevice, sc->stream));
+    }
+    d_key = u_key, tsdf = d_tsdf, obs = d_obs, color = d_color;
+  }
+  DevBuf<int> slot;
+  bool keys_ok = false;
+  EXPCHK(brick_slots_from_keys(*volume, d_key, nbricks, slot, &keys_ok, sc->stream));
+  if (!keys_ok) {
+    EXPCHK(hipStreamSynchronize(sc->stream));
+    return fail(PMVS_EINVAL, "brick_tsdf_mesh: the keys are not strictly ascending inside the grid");
+  }
+  if (pmvs_status st = brick_mesh_device(sc, dev, volume, min_obs, nbricks, d_key, slot.p, tsdf, obs, color, vcap, fcap, buffers,
+                                         nverts, nfaces))
+    return st;
+  EXPCHK(hipStreamSynchronize(sc->stream));  // the uploads and the slot map too, when there were no cells
+  return PMVS_OK;
+}
+
+pmvs_status pmvs_loop_brick_mesh(pmvs_scene* sc, int32_t flags, int32_t first_target, int32_t num_targets,
+                                 const pmvs_brick_params* params, const pmvs_volume* volume, int32_t min_obs, int64_t vcap,
+                                 int64_t fcap, const pmvs_mesh_buffers* buffers, int64_t* nverts, int64_t* nfaces) {
+  if (!mesh_args_ok(min_obs, vcap, fcap, buffers, nverts, nfaces) ||
+      !brick_args_ok(sc, flags, first_target, num_targets, params, volume))
+    return fail(PMVS_EINVAL, "invalid argument");
+  const pmvs_patch* dP = nullptr;
+  int32_t n = 0;
+  if (pmvs_status st = loop_records(sc, "loop_brick_mesh", &dP, &n)) return st;
+  return brick_mesh_records(sc, dP, n, flags, first_target, num_targets, params, volume, min_obs, vcap, fcap, buffers, nverts,
+                            nfaces);
+}
+
+pmvs_status pmvs_brick_mesh_patches(pmvs_scene* sc, const pmvs_patch* patches, int32_t n, int32_t flags, int32_t first_target,
+                                    int32_t num_targets, const pmvs_brick_params* params, const pmvs_volume* volume, int32_t min_obs,
+                                    int64_t vcap, int64_t fcap, const pmvs_mesh_buffers* buffers, int64_t* nverts, int64_t* nfaces) {
+  if (!mesh_args_ok(min_obs, vcap, fcap, buffers, nverts, nfaces) || !records_ok(patches, n) ||
+      !brick_args_ok(sc, flags, first_target, num_targets, params, volume))
+    return fail(PMVS_EINVAL, "invalid argument");
+  CallArena arena;
+  const pmvs_patch* dP = nullptr;
+  if (pmvs_status st = upload_records(sc, patches, n, nullptr, arena, &dP)) return st;
+  return brick_mesh_records(sc, dP, n, flags, first_target, num_targets, params, volume, min_obs, vcap, fcap, buffers, nverts,
+                            nfaces);
 }
 
 // ---- text files (pmvs_text.hip)

@@ -751,8 +751,11 @@ pmvs_status pmvs_write_ply_mesh_binary(const char* path, int64_t nv, const float
   return ofstr.good() ? PMVS_OK : pmvs_io_fail(PMVS_EINVAL, "write failed: %s", path);
 }
 
-// The volume `pmvs2 ... MESH` meshes a cloud in (include/pmvs_amd.h).
-pmvs_status pmvs_volume_from_points(int64_t n, const float* coord, int32_t cells, int32_t pad, pmvs_volume* volume) {
+}  // extern "C"
+
+// The padded bounding box of a cloud as a volume (include/pmvs_amd.h, pmvs_volume_from_points), within the
+// dense limits or the brick volume's.
+static pmvs_status volume_from_points(int64_t n, const float* coord, int32_t cells, int32_t pad, bool brick, pmvs_volume* volume) {
   if (!coord || !volume || n < 1 || cells < 1 || pad < 0) return pmvs_io_fail(PMVS_EINVAL, "invalid argument");
   float lo[3], hi[3];
   for (int a = 0; a < 3; ++a) lo[a] = hi[a] = coord[a];
@@ -768,17 +771,30 @@ pmvs_status pmvs_volume_from_points(int64_t n, const float* coord, int32_t cells
   pmvs_volume v{};
   v.voxel = (float)(ext / (double)cells);
   if (!std::isfinite(v.voxel) || !(v.voxel > 0.0f)) return pmvs_io_fail(PMVS_EINVAL, "volume_from_points: a box of no extent");
-  double voxels = 1.0;
+  double voxels = 1.0, bricks = 1.0;
   for (int a = 0; a < 3; ++a) {
     v.origin[a] = (float)((double)lo[a] - (double)pad * (double)v.voxel);
     const double d = std::max(1.0, std::ceil(((double)hi[a] - (double)lo[a]) / (double)v.voxel)) + 2.0 * (double)pad;
-    if (!std::isfinite(v.origin[a]) || !(d <= 2147483647.0)) return pmvs_io_fail(PMVS_EINVAL, "volume_from_points: too large");
+    if (!std::isfinite(v.origin[a]) || !(d <= (brick ? (double)PMVS_BRICK_MAX_DIM : 2147483647.0)))
+      return pmvs_io_fail(PMVS_EINVAL, "volume_from_points: too large");
     v.dims[a] = (int32_t)d;
     voxels *= d;
+    bricks *= std::ceil(d / (double)PMVS_BRICK);
   }
-  if (voxels > 2147483647.0) return pmvs_io_fail(PMVS_EINVAL, "volume_from_points: more than 2^31-1 voxels");
+  if (!brick && voxels > 2147483647.0) return pmvs_io_fail(PMVS_EINVAL, "volume_from_points: more than 2^31-1 voxels");
+  if (brick && bricks > 2147483647.0) return pmvs_io_fail(PMVS_EINVAL, "volume_from_points: more than 2^31-1 bricks");
   *volume = v;
   return PMVS_OK;
+}
+
+extern "C" {
+
+pmvs_status pmvs_volume_from_points(int64_t n, const float* coord, int32_t cells, int32_t pad, pmvs_volume* volume) {
+  return volume_from_points(n, coord, cells, pad, false, volume);
+}
+
+pmvs_status pmvs_brick_volume_from_points(int64_t n, const float* coord, int32_t cells, int32_t pad, pmvs_volume* volume) {
+  return volume_from_points(n, coord, cells, pad, true, volume);
 }
 
 }  // extern "C"

@@ -219,6 +219,34 @@ hipError_t tsdf_mesh_pass(const pmvs_volume& vol, int min_obs, const float* tsdf
                           const unsigned char* color, long long vcap, long long fcap, const MeshArrays& out, long long* nverts,
                           long long* nfaces, hipStream_t st);
 
+// ---- the sparse volume of 8^3-voxel bricks (pmvs_brick.hip; the definition is csrc/pmvs_brick.h)
+// The bricks the passing pixels of `f` select: one flag byte and one slot (the exclusive sums of the
+// flags) per brick of the grid, and the selected count.  Returns after the stream has finished.
+struct BrickSelection {
+  DevBuf<unsigned char> flag;
+  DevBuf<int> slot;
+  long long bricks = 0, total = 0;  // of the grid, selected
+};
+hipError_t brick_select(const DScene& s, const FuseMaps& f, int first, int count, const pmvs_volume& vol, int margin,
+                        BrickSelection& sel, hipStream_t st);
+// The keys of the first `stored` selected bricks into key[0, stored), ascending; sel.slot becomes the
+// brick -> slot map of those, -1 for every other brick of the grid.  Enqueued on `st`.
+hipError_t brick_keys(BrickSelection& sel, long long stored, long long* key, hipStream_t st);
+// The TSDF of the stored bricks key[0, stored): 512 values per brick and array.  Enqueued on `st`.
+hipError_t brick_integrate(const DScene& s, const FuseMaps& f, int first, int count, const pmvs_volume& vol, float trunc,
+                           const long long* key, long long stored, const TsdfArrays& out, hipStream_t st);
+// The brick -> slot map of a caller's device key list; *ok = strictly ascending and inside the grid
+// (checked by a kernel before anything is written through a key).
+hipError_t brick_slots_from_keys(const pmvs_volume& vol, const long long* key, long long nb, DevBuf<int>& slot, bool* ok,
+                                 hipStream_t st);
+// tsdf_mesh_pass over the virtual volume of the stored bricks (arrays of nb x 512, color may be null).  With
+// more than INT_MAX vertices it writes nothing and reports the counts.  Returns after the stream has
+// finished; its scratch (per stored voxel: flags 2, offset 8, vertex id 4; per vertex and per quad the
+// sort's 32 bytes and storage) is freed by then.
+hipError_t brick_mesh_pass(const pmvs_volume& vol, int min_obs, long long nb, const long long* key, const int* slot, const float* tsdf,
+                           const unsigned char* obs, const unsigned char* color, long long vcap, long long fcap, const MeshArrays& out,
+                           long long* nverts, long long* nfaces, hipStream_t st);
+
 // ---- filter pass (pmvs_filter.hip)
 // The fields of a patch that neighbour and visibility tests read from OTHER patches (isNeighbor,
 // computeGain, isVisible), one 64-B line per patch instead of 2-3 lines of its 1.6-KB record;

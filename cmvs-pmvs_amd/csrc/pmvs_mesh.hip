@@ -7,6 +7,7 @@
 //                          thread and is wave-uniform: each target's projection, optical axis, image size
 //                          and map offset is a scalar load, sum / n / the colour sums stay in registers,
 //                          and the voxel's 9 bytes are written once.  No atomics, no pass per target.
+//                          The per-voxel body is pmvs_tsdf_voxel.h's, shared with the brick kernel.
 //   mesh_cells_kernel      one thread per cell: the active flag (a byte) from the 8 corners
 //   mesh_faces_kernel      one thread per voxel: one bit per axis whose +a edge emits a quad, from the two
 //                          endpoints and the four cells' active flags
@@ -28,6 +29,7 @@
 #include "pmvs_fuse.h"
 #include "pmvs_launch.h"
 #include "pmvs_mesh.h"
+#include "pmvs_tsdf_voxel.h"
 
 namespace pmvsdev {
 namespace {
@@ -44,50 +46,13 @@ struct Dims {
   __host__ __device__ long long cells() const { return (long long)(nx - 1) * (ny - 1) * (nz - 1); }
 };
 
-struct TsdfMapsView {     // the range's depth map and pass flags, by value to the kernel
-  const float* depth;
-  const unsigned char* pass;
-  const long long* off;   // count + 1: the first pixel of each target's map
-  int first, count;       // views [first, first + count)
-};
-
 __global__ __launch_bounds__(256) void tsdf_integrate_kernel(DScene s, TsdfMapsView m, pmvs_volume vol, float trunc,
                                                              TsdfArrays out) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const int nx = vol.dims[0], ny = vol.dims[1], nz = vol.dims[2];
   if (idx >= (long long)nx * ny * nz) return;
   const int i = (int)(idx % nx), j = (int)((idx / nx) % ny), k = (int)(idx / ((long long)nx * ny));
-  const float C4[4] = {pmvsmesh::voxel_centre(vol.origin[0], vol.voxel, i), pmvsmesh::voxel_centre(vol.origin[1], vol.voxel, j),
-                       pmvsmesh::voxel_centre(vol.origin[2], vol.voxel, k), 1.0f};
-  pmvsmesh::VoxelSums v;
-  for (int t = 0; t < m.count; ++t) {  // wave-uniform: the view is read through scalar loads
-    const DView& vw = s.views[m.first + t];
-    const int W = vw.w[s.level], H = vw.h[s.level];
-    float ic[3];
-    project(vw, C4, s.level, ic);
-    int px, py;
-    if (!pmvsfuse::pixel_at(ic[0], ic[1], W, H, &px, &py)) continue;  // the guard of every index below
-    const long long p = (long long)py * W + px;
-    const long long q = m.off[t] + p;
-    if (!m.pass[q]) continue;
-    const float z = depth_of(vw, C4);
-    double sd;
-    if (!(z > 0.0f) || !pmvsmesh::observes(m.depth[q], z, trunc, &sd)) continue;
-    v.sum += pmvsmesh::tsdf_value(sd, trunc);
-    ++v.n;
-    if (pmvsmesh::in_band(sd, trunc)) {
-      const uint32_t w = s.pyr[vw.pyr_off[s.level] + p];
-      v.c[0] += (int)(w & 0xff), v.c[1] += (int)((w >> 8) & 0xff), v.c[2] += (int)((w >> 16) & 0xff);
-      ++v.nc;
-    }
-  }
-  if (out.tsdf) out.tsdf[idx] = pmvsmesh::tsdf_of(v);
-  if (out.obs) out.obs[idx] = pmvsmesh::obs_of(v);
-  if (out.color) {
-    uchar4 c = make_uchar4(0, 0, 0, 0);
-    if (v.nc) c = make_uchar4(pmvsmesh::colour_of(v, 0), pmvsmesh::colour_of(v, 1), pmvsmesh::colour_of(v, 2), 255);
-    reinterpret_cast<uchar4*>(out.color)[idx] = c;
-  }
+  tsdf_store(out, idx, tsdf_voxel(s, m, vol, trunc, i, j, k));
 }
 
 struct VolumeView {

@@ -145,6 +145,14 @@ class MeshBuffers(C.Structure):  # pmvs_mesh_buffers
     _fields_ = [(k, C.c_void_p) for k in ("vertex", "normal", "color", "face")]
 
 
+class BrickParams(C.Structure):  # pmvs_brick_params
+    _fields_ = [("tsdf", TsdfParams), ("margin", C.c_int32)]
+
+
+class BrickBuffers(C.Structure):  # pmvs_brick_buffers
+    _fields_ = [(k, C.c_void_p) for k in ("brick", "tsdf", "obs", "color")]
+
+
 class SeedStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("trial", "pass_", "fail0", "fail1", "refined", "rounds", "candidates",
                                           "reserved")] + [(k, C.c_double) for k in ("wall_ms", "gen_ms", "refine_ms")]
@@ -193,6 +201,8 @@ EXPORTS = ["pmvs_last_error", "pmvs_device_count", "pmvs_scene_create", "pmvs_sc
            "pmvs_loop_fuse", "pmvs_fuse_patches", "pmvs_write_ply_binary",
            "pmvs_loop_tsdf", "pmvs_tsdf_patches", "pmvs_tsdf_mesh", "pmvs_loop_mesh", "pmvs_mesh_patches",
            "pmvs_volume_from_points", "pmvs_write_ply_mesh_binary",
+           "pmvs_loop_brick_tsdf", "pmvs_brick_tsdf_patches", "pmvs_brick_tsdf_mesh", "pmvs_loop_brick_mesh",
+           "pmvs_brick_mesh_patches", "pmvs_brick_volume_from_points",
            "pmvs_loop_text", "pmvs_text_patches", "pmvs_selftest_format", "pmvs_selftest_labels",
            "pmvs_scene_set_shard", "pmvs_scene_set_shard_rccl", "pmvs_scene_set_cluster",
            "pmvs_scene_set_cluster_rccl", "pmvs_rccl_unique_id",
@@ -287,6 +297,15 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.pmvs_loop_mesh.argtypes = [C.c_void_p] + tsdf_tail + mesh_tail
     lib.pmvs_mesh_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32] + tsdf_tail + mesh_tail
     lib.pmvs_volume_from_points.argtypes = [C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Volume)]
+    brick_tail = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(BrickParams), C.POINTER(Volume)]  # flags, range, params, volume
+    brick_caps = [C.c_int64, C.POINTER(BrickBuffers), C.POINTER(C.c_int64)]
+    lib.pmvs_loop_brick_tsdf.argtypes = [C.c_void_p] + brick_tail + brick_caps
+    lib.pmvs_brick_tsdf_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32] + brick_tail + brick_caps
+    lib.pmvs_brick_tsdf_mesh.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Volume), C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p] + mesh_tail[1:]
+    lib.pmvs_loop_brick_mesh.argtypes = [C.c_void_p] + brick_tail + mesh_tail
+    lib.pmvs_brick_mesh_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32] + brick_tail + mesh_tail
+    lib.pmvs_brick_volume_from_points.argtypes = [C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Volume)]
     lib.pmvs_write_ply_mesh_binary.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.pmvs_loop_text.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                    C.POINTER(C.c_int64)]
@@ -631,6 +650,9 @@ class Scene:
     # pmvs_tsdf_buffers: the volume's nx x ny x nz voxels; pmvs_mesh_buffers: v vertices, f faces
     TSDF_ARRAYS = {"tsdf": ("float32", ("nz", "ny", "nx")), "obs": ("uint8", ("nz", "ny", "nx")),
                    "color": ("uint8", ("nz", "ny", "nx", 4))}
+    # pmvs_brick_buffers: b stored bricks of 8 x 8 x 8 voxels, [lk, lj, li]
+    BRICK_ARRAYS = {"brick": ("int64", ("b",)), "tsdf": ("float32", ("b", 8, 8, 8)), "obs": ("uint8", ("b", 8, 8, 8)),
+                    "color": ("uint8", ("b", 8, 8, 8, 4))}
     MESH_ARRAYS = {"vertex": ("float32", ("v", 3)), "normal": ("float32", ("v", 3)), "color": ("uint8", ("v", 3)),
                    "face": ("int32", ("f", 3))}
 
@@ -895,6 +917,90 @@ class Scene:
         return self._mesh_call(lambda *a: self.lib.pmvs_mesh_patches(self.handle, _ptr(pa), len(pa), *shared, min_obs, *a),
                                device, arrays)
 
+    def _brick_params(self, volume, trunc, margin, writer_order, device, first_target, num_targets, radius, min_support,
+                      depth_rel, normal_cos):
+        """(flags, first, num, byref(params), byref(volume)): the arguments the brick calls share."""
+        num, radius = self._range(first_target, num_targets, radius)
+        prm = BrickParams(TsdfParams(FuseParams(radius, min_support, depth_rel, normal_cos), trunc), margin)
+        return self._flags(writer_order, device), first_target, num, C.byref(prm), C.byref(volume)
+
+    def _brick_call(self, call, device, arrays):
+        """call(bcap, byref(buffers), byref(nbricks)): a counting call, then the arrays."""
+        nb = C.c_int64(0)
+        _check(call(0, C.byref(BrickBuffers()), C.byref(nb)))
+        b = int(nb.value)
+        out, buf = self._new_arrays(BrickBuffers, self.BRICK_ARRAYS, arrays, device, b=b)
+        _check(call(b, C.byref(buf), C.byref(nb)))
+        if int(nb.value) != b:
+            raise PmvsError(f"the volume has {nb.value} bricks after counting {b}")
+        return out
+
+    def loop_brick_tsdf(self, volume: Volume, trunc: float, margin: int, writer_order: bool = True, device: bool = False,
+                        arrays=None, first_target: int = 0, num_targets=None, radius=None, min_support: int = 2,
+                        depth_rel: float = 0.01, normal_cos: float = 0.5) -> dict:
+        """pmvs_loop_brick_tsdf: loop_tsdf in a sparse volume of 8 x 8 x 8-voxel bricks: only the bricks within
+        `margin` voxels of a fused point's voxel exist.  Keyed by the fields of pmvs_brick_buffers: brick [b]
+        int64 (the keys (bk * By + bj) * Bx + bi of the stored bricks, ascending), tsdf and obs [b, 8, 8, 8]
+        ([lk, lj, li]; loop_tsdf's values for the voxels inside the volume, (1, 0) for an edge brick's
+        overhang), color [b, 8, 8, 8, 4].  `volume` may exceed loop_tsdf's 2^31-1 voxels.  The arrays are
+        sized by a counting call first, which selects the bricks too."""
+        shared = self._brick_params(volume, trunc, margin, writer_order, device, first_target, num_targets, radius,
+                                    min_support, depth_rel, normal_cos)
+        return self._brick_call(lambda *a: self.lib.pmvs_loop_brick_tsdf(self.handle, *shared, *a), device, arrays)
+
+    def brick_tsdf_patches(self, patches: np.ndarray, volume: Volume, trunc: float, margin: int, writer_order: bool = True,
+                           device: bool = False, arrays=None, first_target: int = 0, num_targets=None, radius=None,
+                           min_support: int = 2, depth_rel: float = 0.01, normal_cos: float = 0.5) -> dict:
+        """pmvs_brick_tsdf_patches: loop_brick_tsdf's arrays for caller-supplied PATCH_DTYPE records."""
+        pa = self._records(patches)
+        shared = self._brick_params(volume, trunc, margin, writer_order, device, first_target, num_targets, radius,
+                                    min_support, depth_rel, normal_cos)
+        return self._brick_call(lambda *a: self.lib.pmvs_brick_tsdf_patches(self.handle, _ptr(pa), len(pa), *shared, *a),
+                                device, arrays)
+
+    def brick_tsdf_mesh(self, volume: Volume, brick, tsdf, obs, color=None, min_obs: int = 1, device: bool = False,
+                        arrays=None) -> dict:
+        """pmvs_brick_tsdf_mesh: tsdf_mesh of the virtual volume made of the bricks `brick` (keys, strictly
+        ascending; tsdf and obs [b, 8, 8, 8], color [b, 8, 8, 8, 4] or None), in which a voxel of no brick is
+        unobserved: tsdf_mesh's arrays, byte for byte those of the bricks scattered into a dense volume.
+        device=True: the brick arrays are torch tensors on the scene's device and so is the mesh."""
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            ins = [torch.as_tensor(a, dtype=dt, device=dev).contiguous() if a is not None else None
+                   for a, dt in ((brick, torch.int64), (tsdf, torch.float32), (obs, torch.uint8), (color, torch.uint8))]
+            sizes = [0 if a is None else a.numel() for a in ins]
+            ptrs = [None if a is None or not a.numel() else a.data_ptr() for a in ins]
+        else:
+            ins = [np.ascontiguousarray(a, dt) if a is not None else None
+                   for a, dt in ((brick, np.int64), (tsdf, np.float32), (obs, np.uint8), (color, np.uint8))]
+            sizes, ptrs = [0 if a is None else a.size for a in ins], [_ptr(a) for a in ins]
+        b = sizes[0]
+        if sizes[1:3] != [512 * b, 512 * b] or sizes[3] not in (0, 2048 * b):
+            raise ValueError("brick_tsdf_mesh: the arrays do not have the bricks' size")
+        flags = self._flags(False, device)
+        return self._mesh_call(lambda *a: self.lib.pmvs_brick_tsdf_mesh(self.handle, flags, C.byref(volume), min_obs, b, *ptrs, *a),
+                               device, arrays)
+
+    def loop_brick_mesh(self, volume: Volume, trunc: float, margin: int, min_obs: int = 1, writer_order: bool = True,
+                        device: bool = False, arrays=None, first_target: int = 0, num_targets=None, radius=None,
+                        min_support: int = 2, depth_rel: float = 0.01, normal_cos: float = 0.5) -> dict:
+        """pmvs_loop_brick_mesh: loop_brick_tsdf then brick_tsdf_mesh in one call, the bricks never leaving
+        the device; tsdf_mesh's arrays.  The counting call selects and integrates too, so both run twice."""
+        shared = self._brick_params(volume, trunc, margin, writer_order, device, first_target, num_targets, radius,
+                                    min_support, depth_rel, normal_cos)
+        return self._mesh_call(lambda *a: self.lib.pmvs_loop_brick_mesh(self.handle, *shared, min_obs, *a), device, arrays)
+
+    def brick_mesh_patches(self, patches: np.ndarray, volume: Volume, trunc: float, margin: int, min_obs: int = 1,
+                           writer_order: bool = True, device: bool = False, arrays=None, first_target: int = 0, num_targets=None,
+                           radius=None, min_support: int = 2, depth_rel: float = 0.01, normal_cos: float = 0.5) -> dict:
+        """pmvs_brick_mesh_patches: loop_brick_mesh's arrays for caller-supplied PATCH_DTYPE records."""
+        pa = self._records(patches)
+        shared = self._brick_params(volume, trunc, margin, writer_order, device, first_target, num_targets, radius,
+                                    min_support, depth_rel, normal_cos)
+        return self._mesh_call(lambda *a: self.lib.pmvs_brick_mesh_patches(self.handle, _ptr(pa), len(pa), *shared, min_obs, *a),
+                               device, arrays)
+
     def _text(self, call, writer_order, index2image, device: bool, out):
         """call(flags, index2image, out, cap, byref(size)): a size query, the buffer (numpy uint8, or a torch
         uint8 tensor on the scene's device; `out` supplies it) and the call that fills it; returns the
@@ -1129,6 +1235,15 @@ def volume_from_points(coord, cells: int = 256, pad: int = 3) -> Volume:
     c = np.ascontiguousarray(coord, np.float32).reshape(-1, 3)
     v = Volume()
     _check(load_library().pmvs_volume_from_points(len(c), _ptr(c), cells, pad, C.byref(v)))
+    return v
+
+
+def brick_volume_from_points(coord, cells: int, pad: int = 3) -> Volume:
+    """pmvs_brick_volume_from_points: volume_from_points within the brick volume's limits (dims up to 2^20, a
+    brick grid up to 2^31-1): the volume `pmvs2 ... FINEMESH` meshes a cloud in."""
+    c = np.ascontiguousarray(coord, np.float32).reshape(-1, 3)
+    v = Volume()
+    _check(load_library().pmvs_brick_volume_from_points(len(c), _ptr(c), cells, pad, C.byref(v)))
     return v
 
 

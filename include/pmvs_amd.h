@@ -654,6 +654,102 @@ pmvs_status pmvs_volume_from_points(int64_t n, const float* coord, int32_t cells
 pmvs_status pmvs_write_ply_mesh_binary(const char* path, int64_t nv, const float* vertex, const float* normal,
                                        const uint8_t* color, int64_t nf, const int32_t* face);
 
+/* The same meshing in a SPARSE volume: the volume exists only in 8 x 8 x 8-voxel bricks near the fused
+ * points, so its resolution is bounded by the surface's area and not by the box's volume.  A voxel's values
+ * and the mesh keep the definitions above exactly; what follows defines where the volume exists
+ * (csrc/pmvs_brick.h implements it once, for host and device).
+ *
+ * THE VIRTUAL VOLUME is a pmvs_volume with limits of its own: every dim in 1..PMVS_BRICK_MAX_DIM, and the
+ * brick grid Ba = ceil(dims[a] / 8) with Bx*By*Bz <= 2^31-1; the dense nx*ny*nz limit does not apply.  The
+ * key of brick (bi, bj, bk) is (bk*By + bj)*Bx + bi.  The stored bricks are listed by ascending key; voxel
+ * (8bi+li, 8bj+lj, 8bk+lk) of stored brick number s (its position in that list) is at array index
+ * s*512 + (lk*8 + lj)*8 + li.
+ *
+ * SELECTION (which bricks exist).
+ *  1. For every pixel p of the range with pass(p) (fuse step 4): Sf from fuse step 2.
+ *  2. g_a = floor(((double)Sf[a] - (double)origin[a]) / (double)voxel) per axis, in double.
+ *  3. The pixel is skipped if, compared in double, g_a + margin < 0 or g_a - margin > dims[a] - 1 for any a.
+ *  4. Otherwise lo_a = max(0, g_a - margin), hi_a = min(dims[a] - 1, g_a + margin).
+ *  5. Every brick with lo_a >> 3 <= b_a <= hi_a >> 3 on all three axes is selected.
+ * The brick list is the selected keys in ascending order.  Nothing depends on the order of the work.
+ *
+ * INTEGRATION (pmvs_loop_brick_tsdf, pmvs_brick_tsdf_patches).  A stored voxel inside dims gets steps 1-3
+ * of the INTEGRATION above, by the same code: the bytes pmvs_loop_tsdf writes for that voxel whenever the
+ * dense call accepts the volume.  A stored voxel outside dims (the overhang of an edge brick) is tsdf 1.0f,
+ * obs 0, colour (0, 0, 0, 0).  *nbricks receives the full count; only the first min(count, bcap) bricks are
+ * written and nothing past them; bcap 0 with NULL arrays is the counting call.
+ *
+ * EXTRACTION (pmvs_brick_tsdf_mesh).  The EXTRACTION above applied to the virtual volume, in which a voxel
+ * of no stored brick reads as obs 0, tsdf 1.0f, colour 0: the same cells, edges, vertex, normal, colour and
+ * face rules and the same orders, vertices by ascending virtual cell index ((k*(ny-1))+j)*(nx-1) + i and
+ * faces by ascending (virtual voxel index, axis).  So for any volume the dense calls accept, the output is
+ * byte for byte that of pmvs_tsdf_mesh on the dense arrays obtained by scattering the bricks into a volume
+ * pre-filled with (1.0f, 0, 0).  Keys are caller-supplied here: strictly ascending and inside the grid.
+ * More than 2^31-1 vertices: PMVS_EUNSUPPORTED (face ids are int32).
+ *
+ * MARGIN is the caller's knob, not a guarantee: a cell that is active in the dense volume but has a corner
+ * in no stored brick drops out, and the surface opens a boundary there -- the rule for unobserved regions.
+ * A margin of ceil(trunc / voxel) + 2 keeps the band around every fused point; `pmvs2 ... FINEMESH` uses it.
+ *
+ * flags, the target range, record validation, the loop's result and device / host mode are those of the
+ * dense calls; pmvs_brick_tsdf_mesh takes of the flags only PMVS_EXPORT_DEVICE.  pmvs_loop_brick_mesh /
+ * pmvs_brick_mesh_patches select, integrate and extract in one call and the bricks never leave the device.
+ * As in the dense calls, a counting call does the whole selection (and the mesh calls the integration)
+ * again: no volume is kept between calls.
+ * PMVS_EINVAL: the dense calls' checks with the volume limits above in place of theirs; a margin outside
+ * 0..PMVS_BRICK_MAX_MARGIN; a negative cap or nbricks; pmvs_brick_tsdf_mesh: a NULL brick, tsdf or obs with
+ * nbricks > 0, keys not strictly ascending or outside the grid (device mode: checked by a kernel before a
+ * key is used).  PMVS_ENOMEM when the device cannot hold the scratch: the integration's 22 bytes per pixel
+ * of the range; 5 bytes per brick of the GRID (flag 1, slot 4; pmvs_brick_tsdf_mesh: 4) and the scan's
+ * storage; the bricks themselves (8 + 512 * 9 bytes each: the combined calls hold all of them, the others
+ * the requested arrays in host mode); for the extraction 10 bytes per stored voxel (cell flag 1, face flags
+ * 1, offset 8), 4 more (vertex id) when faces are written, and 32 bytes per vertex, then per quad, for the
+ * sort's (key, value) pairs in and out plus rocprim's radix sort storage; in host mode the requested mesh
+ * arrays.  All of it is allocated for the call and freed on return. */
+#define PMVS_BRICK 8              /* voxels per brick edge; 512 per brick */
+#define PMVS_BRICK_MAX_MARGIN 64
+#define PMVS_BRICK_MAX_DIM (1 << 20)
+
+typedef struct pmvs_brick_params {
+  pmvs_tsdf_params tsdf;    /* the maps integrated and the truncation distance */
+  int32_t          margin;  /* 0..PMVS_BRICK_MAX_MARGIN: voxels around each fused point's voxel */
+} pmvs_brick_params;
+
+typedef struct pmvs_brick_buffers {  /* any pointer may be NULL: that array is skipped */
+  int64_t* brick;   /* bcap: brick keys, strictly ascending */
+  float*   tsdf;    /* bcap x 512 */
+  uint8_t* obs;     /* bcap x 512 */
+  uint8_t* color;   /* bcap x 512 x 4: RGBA as pmvs_tsdf_buffers; a device pointer is 4-byte aligned */
+} pmvs_brick_buffers;
+
+/* Reads the result pmvs_run_loop left on the device and does not consume it. */
+pmvs_status pmvs_loop_brick_tsdf(pmvs_scene* scene, int32_t flags, int32_t first_target, int32_t num_targets,
+                                 const pmvs_brick_params* params, const pmvs_volume* volume, int64_t bcap,
+                                 const pmvs_brick_buffers* buffers, int64_t* nbricks);
+/* The same for caller-supplied records. */
+pmvs_status pmvs_brick_tsdf_patches(pmvs_scene* scene, const pmvs_patch* patches, int32_t n, int32_t flags,
+                                    int32_t first_target, int32_t num_targets, const pmvs_brick_params* params,
+                                    const pmvs_volume* volume, int64_t bcap, const pmvs_brick_buffers* buffers,
+                                    int64_t* nbricks);
+/* The mesh of caller-supplied bricks (brick nbricks keys, tsdf and obs nbricks x 512, color nbricks x 512 x 4
+ * or NULL; a device color pointer is 4-byte aligned). */
+pmvs_status pmvs_brick_tsdf_mesh(pmvs_scene* scene, int32_t flags, const pmvs_volume* volume, int32_t min_obs,
+                                 int64_t nbricks, const int64_t* brick, const float* tsdf, const uint8_t* obs,
+                                 const uint8_t* color, int64_t vcap, int64_t fcap, const pmvs_mesh_buffers* buffers,
+                                 int64_t* nverts, int64_t* nfaces);
+/* Selection, integration, then extraction. */
+pmvs_status pmvs_loop_brick_mesh(pmvs_scene* scene, int32_t flags, int32_t first_target, int32_t num_targets,
+                                 const pmvs_brick_params* params, const pmvs_volume* volume, int32_t min_obs,
+                                 int64_t vcap, int64_t fcap, const pmvs_mesh_buffers* buffers, int64_t* nverts,
+                                 int64_t* nfaces);
+pmvs_status pmvs_brick_mesh_patches(pmvs_scene* scene, const pmvs_patch* patches, int32_t n, int32_t flags,
+                                    int32_t first_target, int32_t num_targets, const pmvs_brick_params* params,
+                                    const pmvs_volume* volume, int32_t min_obs, int64_t vcap, int64_t fcap,
+                                    const pmvs_mesh_buffers* buffers, int64_t* nverts, int64_t* nfaces);
+/* pmvs_volume_from_points' formulas within the brick volume's limits (a dim past PMVS_BRICK_MAX_DIM or a
+ * brick grid past 2^31-1 is PMVS_EINVAL): the volume `pmvs2 ... FINEMESH` uses. */
+pmvs_status pmvs_brick_volume_from_points(int64_t n, const float* coord, int32_t cells, int32_t pad, pmvs_volume* volume);
+
 /* The .ply / .patch / .pset text of the model, formatted on the device: the bytes pmvs_write_ply /
  * pmvs_write_patches / pmvs_write_pset write from the export of the same records and flags
  * (CPatchOrganizerS::writePLY patchOrganizerS.cpp:687-776, writePatches2 :89-132 with Patch::operator<<
