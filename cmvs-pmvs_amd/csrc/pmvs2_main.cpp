@@ -1,4 +1,4 @@
-// pmvs2_main.cpp -- the `pmvs2 prefix option_file [PATCH] [PSET] [DEPTH] [PIXDEPTH] [FUSE] [MESH] [FINEMESH]` executable (reference
+// pmvs2_main.cpp -- the `pmvs2 prefix option_file [PATCH] [PSET] [DEPTH] [PIXDEPTH] [FUSE] [MESH] [FINEMESH] [TEXMESH]` executable (reference
 // source/pmvs.cpp:7-63 with CFindMatch::init / run / write, findMatch.cpp:30-224), driving the
 // MI355X-native core through its C-ABI (include/pmvs_amd.h).  A drop-in for the program
 // genOption's pmvs.sh calls (genOption.cpp:73): same arguments, same input tree
@@ -36,6 +36,8 @@
 #include <string>
 #include <thread>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>
 
 #include "../../include/pmvs_amd.h"
 
@@ -126,7 +128,7 @@ void usage(const char* argv0) {
             << "oimages  5  0 2 4 6 8 (enumeration)" << std::endl
             << "        -1  24 48 (range specification)" << std::endl
             << std::endl
-            << "[Optional export] PATCH PSET DEPTH PIXDEPTH FUSE MESH FINEMESH" << std::endl
+            << "[Optional export] PATCH PSET DEPTH PIXDEPTH FUSE MESH FINEMESH TEXMESH" << std::endl
             << " i.e export patch and pset: prefix option_file PATCH PSET"
             << " i.e export patch only: prefix option_file PATCH" << std::endl
             << " DEPTH: every target image's depth map, one value per csize x csize cell, as" << std::endl
@@ -145,7 +147,12 @@ void usage(const char* argv0) {
             << " FINEMESH: the same mesh at image resolution, in a sparse volume of 8x8x8-voxel bricks that exists only" << std::endl
             << "        within 5 voxels of the fused points: voxel = the cloud's longest extent / min(4096, the largest" << std::endl
             << "        width or height of the target images at the level), truncation 3 voxels, as the binary PLY" << std::endl
-            << "        models/option_file.finemesh.ply" << std::endl;
+            << "        models/option_file.finemesh.ply" << std::endl
+            << " TEXMESH: MESH's mesh textured from the target images themselves (no atlas): every face gets the target" << std::endl
+            << "        that sees it from the front with the largest projected area and whose view of its three corners" << std::endl
+            << "        the mesh itself does not block (within 1 % of the depth), as the binary PLY" << std::endl
+            << "        models/option_file.texmesh.ply with one `comment TextureFile ../visualize/<image>` per target" << std::endl
+            << "        image, per-face texcoord (u, v in [0, 1], v up) and texnumber (-1 = no image sees the face)" << std::endl;
 }
 
 }  // namespace
@@ -159,7 +166,7 @@ int main(int argc, char* argv[]) {
   std::cout << std::endl;
   const std::string prefix = argv[1], option = argv[2];
   bool export_patch = false, export_pset = false, export_depth = false, export_pixdepth = false, export_fuse = false, export_mesh = false,
-       export_finemesh = false;
+       export_finemesh = false, export_texmesh = false;
   for (int i = 3; i < argc; ++i) {
     if (std::string(argv[i]) == "PATCH") export_patch = true;
     if (std::string(argv[i]) == "PSET") export_pset = true;
@@ -168,6 +175,7 @@ int main(int argc, char* argv[]) {
     if (std::string(argv[i]) == "FUSE") export_fuse = true;
     if (std::string(argv[i]) == "MESH") export_mesh = true;
     if (std::string(argv[i]) == "FINEMESH") export_finemesh = true;
+    if (std::string(argv[i]) == "TEXMESH") export_texmesh = true;
   }
   const double t0 = now_s();
 
@@ -203,6 +211,7 @@ int main(int argc, char* argv[]) {
   // the views one after the other; here a pool of host threads decodes them (PMVS_IO_THREADS, default
   // min(16, cores)), and failures are reported in view order as the serial loop would.
   std::vector<View> views(num);
+  std::vector<std::string> tex_names(num);  // the image files as models/ sees them (TEXMESH)
   std::vector<std::string> errors(num);
   std::vector<pmvs_status> status(num, PMVS_OK);
   std::cerr << "Reading images: " << std::flush;
@@ -217,6 +226,7 @@ int main(int argc, char* argv[]) {
       const std::string id = (exists(v8 + ".ppm") || exists(v8 + ".jpg")) ? b8 : b4;
       View& v = views[index];
       const std::string name = complete_name(prefix + "visualize/" + id, true);
+      tex_names[index] = "../visualize/" + name.substr(prefix.size() + std::strlen("visualize/"));
       pmvs_status st;
       errors[index] = "image";
       if ((st = pmvs_image_load(name.c_str(), &v.w, &v.h, nullptr))) return st;
@@ -319,6 +329,8 @@ int main(int argc, char* argv[]) {
       CHECK("cluster", pmvs_scene_set_cluster(sc, job.rank, job.world, images.data(), &pmvs_tcp_allgather, job.tcp));
     }
   }
+  std::vector<int32_t> tex_dims((size_t)tnum * 2);  // the level-0 sizes of the target images (TEXMESH)
+  for (int t = 0; t < tnum; ++t) tex_dims[2 * t] = views[t].w, tex_dims[2 * t + 1] = views[t].h;
   std::vector<View>().swap(views);  // level-0 images live on the device now
   const double t_init = now_s();
 
@@ -468,7 +480,7 @@ int main(int argc, char* argv[]) {
       CHECK("pfm", pmvs_write_pfm((out + name).c_str(), dims[0], dims[1], depth.data()));
     }
   }
-  if (export_fuse || export_mesh || export_finemesh) {
+  if (export_fuse || export_mesh || export_finemesh || export_texmesh) {
     // the model just written fused over all target images (pmvs_loop_fuse, writer order): a counting
     // call sizes the host arrays
     pmvs_fuse_params fp{};
@@ -541,6 +553,62 @@ int main(int argc, char* argv[]) {
       }
       CHECK("fine mesh ply", pmvs_write_ply_mesh_binary((out + ".finemesh.ply").c_str(), nv, vertex.data(), vnormal.data(),
                                                         vcolor.data(), nf, face.data()));
+    }
+    if (export_texmesh) {
+      // MESH's mesh (the same volume and parameters) obtained in device mode and kept there, a target chosen
+      // per face over all target images (pmvs_mesh_texture), then one fetch and one write
+      int64_t nv = 0, nf = 0;
+      std::vector<float> vertex, vnormal, uv;
+      std::vector<uint8_t> vcolor;
+      std::vector<int32_t> face, view;
+      pmvs_volume vol{};
+      if (npts > 0 && pmvs_volume_from_points(npts, coord.data(), 256, 3, &vol) == PMVS_OK) {
+        const int32_t flags = PMVS_EXPORT_WRITER_ORDER | PMVS_EXPORT_DEVICE;
+        pmvs_tsdf_params tp{};
+        tp.fuse = fp;
+        tp.trunc = 3.0f * vol.voxel;
+        pmvs_mesh_buffers mb{};
+        CHECK("textured mesh", pmvs_loop_mesh(sc, flags, 0, tnum, &tp, &vol, 1, 0, 0, &mb, &nv, &nf));
+        const size_t vb = (size_t)std::max<int64_t>(nv, 1) * 3, fb3 = (size_t)std::max<int64_t>(nf, 1) * 3;
+        // one device block: vertex, normal, uv (float), face, view (int32), colour (bytes)
+        const size_t off_normal = vb * 4, off_uv = off_normal + vb * 4, off_face = off_uv + fb3 * 2 * 4, off_view = off_face + fb3 * 4,
+                     off_color = off_view + fb3 / 3 * 4, bytes = off_color + vb;
+        char* block = nullptr;
+        if (hipSetDevice(job.device) != hipSuccess || hipMalloc((void**)&block, bytes) != hipSuccess) {
+          std::cerr << "pmvs2: textured mesh: " << bytes << " bytes of device memory" << std::endl;
+          return 1;
+        }
+        mb.vertex = (float*)block, mb.normal = (float*)(block + off_normal), mb.color = (uint8_t*)(block + off_color);
+        mb.face = (int32_t*)(block + off_face);
+        int64_t wv = 0, wf = 0;
+        CHECK("textured mesh", pmvs_loop_mesh(sc, flags, 0, tnum, &tp, &vol, 1, nv, nf, &mb, &wv, &wf));
+        nv = std::min(nv, wv), nf = std::min(nf, wf);
+        pmvs_texture_params xp{};
+        xp.depth_rel = fp.depth_rel;  // the fusion's 1 %
+        xp.min_area = 0.0f;
+        pmvs_texture_buffers tb{};
+        tb.view = (int32_t*)(block + off_view), tb.uv = (float*)(block + off_uv);
+        CHECK("texture", pmvs_mesh_texture(sc, PMVS_EXPORT_DEVICE, 0, tnum, &xp, nv, mb.vertex, nf, mb.face, &tb));
+        std::vector<char> host(bytes);
+        if (hipMemcpy(host.data(), block, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
+          std::cerr << "pmvs2: textured mesh: the fetch failed" << std::endl;
+          return 1;
+        }
+        (void)hipFree(block);
+        vertex.resize((size_t)nv * 3), vnormal.resize((size_t)nv * 3), vcolor.resize((size_t)nv * 3);
+        face.resize((size_t)nf * 3), view.resize((size_t)nf), uv.resize((size_t)nf * 6);
+        std::memcpy(vertex.data(), host.data(), vertex.size() * 4);
+        std::memcpy(vnormal.data(), host.data() + off_normal, vnormal.size() * 4);
+        std::memcpy(vcolor.data(), host.data() + off_color, vcolor.size());
+        std::memcpy(face.data(), host.data() + off_face, face.size() * 4);
+        std::memcpy(view.data(), host.data() + off_view, view.size() * 4);
+        std::memcpy(uv.data(), host.data() + off_uv, uv.size() * 4);
+      }
+      std::vector<const char*> names((size_t)tnum);
+      for (int t = 0; t < tnum; ++t) names[t] = tex_names[t].c_str();
+      CHECK("textured mesh ply",
+            pmvs_write_ply_texmesh_binary((out + ".texmesh.ply").c_str(), nv, vertex.data(), vnormal.data(), vcolor.data(), nf, face.data(),
+                                          view.data(), uv.data(), tnum, names.data(), tex_dims.data()));
     }
   }
   pmvs_scene_destroy(sc);

@@ -2130,6 +2130,85 @@ pmvs_status pmvs_brick_mesh_patches(pmvs_scene* sc, const pmvs_patch* patches, i
                             nfaces);
 }
 
+// ---- the mesh rasterised into the targets and a view per face (pmvs_texmesh.hip)
+namespace {
+bool texture_params_ok(const pmvs_texture_params* p) {
+  return p && std::isfinite(p->depth_rel) && p->depth_rel >= 0.0f && std::isfinite(p->min_area) && p->min_area >= 0.0f;
+}
+
+// What both calls check of the mesh and the scene; the scene last (range_call_ok).
+bool texmesh_args_ok(const pmvs_scene* sc, int32_t flags, int32_t first, int32_t num, int64_t nv, const float* vertex, int64_t nf,
+                     const int32_t* face) {
+  return nv >= 0 && nv <= INT32_MAX && nf >= 0 && nf <= INT32_MAX && (nv == 0 || vertex) && (nf == 0 || face) &&
+         flags_ok(flags, PMVS_EXPORT_DEVICE) && range_call_ok(sc, flags, first, num);
+}
+
+// The mesh on the device: the caller's pointers in device mode, uploaded into the arena otherwise.  Host ids
+// are checked here before the scene is touched, device ids by a kernel before any of them is an index.
+pmvs_status texmesh_device_mesh(pmvs_scene* sc, bool dev, const char* call, int64_t nv, const float* vertex, int64_t nf,
+                                const int32_t* face, CallArena& arena, const float** d_vertex, const int** d_face) {
+  *d_vertex = vertex, *d_face = face;
+  if (!dev)
+    for (int64_t i = 0; i < 3 * nf; ++i)
+      if (face[i] < 0 || face[i] >= nv) return fail(PMVS_EINVAL, "%s: face %lld has a vertex id outside [0, nv)", call, (long long)(i / 3));
+  HIPCHK(hipSetDevice(sc->device));
+  if (!dev) {
+    float* uv = nullptr;
+    int* uf = nullptr;
+    EXPCHK(arena.alloc(&uv, (size_t)nv * 3));
+    EXPCHK(arena.alloc(&uf, (size_t)nf * 3));
+    if (nv) EXPCHK(hipMemcpyAsync(uv, vertex, (size_t)nv * 3 * sizeof(float), hipMemcpyHostToDevice, sc->stream));
+    if (nf) EXPCHK(hipMemcpyAsync(uf, face, (size_t)nf * 3 * sizeof(int), hipMemcpyHostToDevice, sc->stream));
+    *d_vertex = uv, *d_face = uf;
+  } else {
+    bool ids_ok = true;
+    EXPCHK(mesh_ids_check(face, nf, nv, &ids_ok, sc->stream));
+    if (!ids_ok) return fail(PMVS_EINVAL, "%s: a face has a vertex id outside [0, nv)", call);
+  }
+  return PMVS_OK;
+}
+}  // namespace
+
+pmvs_status pmvs_mesh_raster(pmvs_scene* sc, int32_t flags, int32_t first_target, int32_t num_targets, int64_t nv,
+                             const float* vertex, int64_t nf, const int32_t* face, const pmvs_raster_buffers* buffers) {
+  if (!buffers || !texmesh_args_ok(sc, flags, first_target, num_targets, nv, vertex, nf, face))
+    return fail(PMVS_EINVAL, "invalid argument");
+  const bool dev = (flags & PMVS_EXPORT_DEVICE) != 0;
+  CallArena arena;
+  const float* d_vertex = nullptr;
+  const int* d_face = nullptr;
+  if (pmvs_status st = texmesh_device_mesh(sc, dev, "mesh_raster", nv, vertex, nf, face, arena, &d_vertex, &d_face)) return st;
+  const size_t pixels = (size_t)pixel_map_layout(sc, first_target, num_targets, nullptr, nullptr);
+  Staging stg(arena, dev);
+  RasterArrays a;
+  EXPCHK(stg.fixed(&a.face, buffers->face, pixels));
+  EXPCHK(stg.fixed(&a.depth, buffers->depth, pixels));
+  EXPCHK(mesh_raster_pass(sc->ds, sc->hviews.data(), first_target, num_targets, d_vertex, nf, d_face, a, sc->stream));
+  EXPCHK(stg.finish(sc->stream, true));  // in device mode too: the uploads' arena is freed on return
+  return PMVS_OK;
+}
+
+pmvs_status pmvs_mesh_texture(pmvs_scene* sc, int32_t flags, int32_t first_target, int32_t num_targets,
+                              const pmvs_texture_params* params, int64_t nv, const float* vertex, int64_t nf,
+                              const int32_t* face, const pmvs_texture_buffers* buffers) {
+  if (!buffers || !texture_params_ok(params) || !texmesh_args_ok(sc, flags, first_target, num_targets, nv, vertex, nf, face))
+    return fail(PMVS_EINVAL, "invalid argument");
+  if (nf == 0) return PMVS_OK;  // no face: nothing is written
+  const bool dev = (flags & PMVS_EXPORT_DEVICE) != 0;
+  CallArena arena;
+  const float* d_vertex = nullptr;
+  const int* d_face = nullptr;
+  if (pmvs_status st = texmesh_device_mesh(sc, dev, "mesh_texture", nv, vertex, nf, face, arena, &d_vertex, &d_face)) return st;
+  Staging stg(arena, dev);
+  TextureArrays a;
+  EXPCHK(stg.fixed(&a.view, buffers->view, (size_t)nf));
+  EXPCHK(stg.fixed(&a.uv, buffers->uv, (size_t)nf * 6));
+  EXPCHK(stg.fixed(&a.score, buffers->score, (size_t)nf));
+  EXPCHK(mesh_texture_pass(sc->ds, sc->hviews.data(), first_target, num_targets, *params, d_vertex, nf, d_face, a, sc->stream));
+  EXPCHK(stg.finish(sc->stream, true));
+  return PMVS_OK;
+}
+
 // ---- text files (pmvs_text.hip)
 namespace {
 bool text_args_ok(const pmvs_scene* sc, int32_t kind, int32_t flags, const char* out, int64_t cap, const int64_t* bytes) {

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/pmvs_amd.h"
+#include "pmvs_texmesh.h"
 
 // libjpeg's API types (the image's libjpeg 9 headers); the library itself is loaded at run time
 // (dlopen), so the product has no link-time JPEG dependency and reports PMVS_EUNSUPPORTED for
@@ -747,6 +748,69 @@ pmvs_status pmvs_write_ply_mesh_binary(const char* path, int64_t nv, const float
       for (int k = 0; k < 3; ++k) put32(rec + 1 + 4 * k, (uint32_t)face[3 * (p0 + i) + k]);
     }
     ofstr.write(buf.data(), (std::streamsize)(13 * m));
+  }
+  return ofstr.good() ? PMVS_OK : pmvs_io_fail(PMVS_EINVAL, "write failed: %s", path);
+}
+
+// A textured mesh (pmvs_mesh_texture) as binary little-endian PLY: the mesh writer's header with the
+// TextureFile comments and the per-face texcoord / texnumber; 27-byte vertex records, 42-byte face records.
+pmvs_status pmvs_write_ply_texmesh_binary(const char* path, int64_t nv, const float* vertex, const float* normal,
+                                          const uint8_t* color, int64_t nf, const int32_t* face, const int32_t* view,
+                                          const float* uv, int32_t ntex, const char* const* tex_files, const int32_t* tex_dims) {
+  if (!path || nv < 0 || nf < 0 || ntex < 0 || (nv > 0 && (!vertex || !normal || !color)) || (nf > 0 && (!face || !view || !uv)) ||
+      (ntex > 0 && (!tex_files || !tex_dims)))
+    return pmvs_io_fail(PMVS_EINVAL, "invalid argument");
+  for (int32_t t = 0; t < ntex; ++t)
+    if (!tex_files[t] || tex_dims[2 * t] < 1 || tex_dims[2 * t + 1] < 1)
+      return pmvs_io_fail(PMVS_EINVAL, "write_ply_texmesh_binary: texture %d has no name or no extent", (int)t);
+  for (int64_t f = 0; f < nf; ++f)
+    if (view[f] < -1 || view[f] >= ntex)
+      return pmvs_io_fail(PMVS_EINVAL, "write_ply_texmesh_binary: face %lld has view %d of %d textures", (long long)f, (int)view[f],
+                          (int)ntex);
+  std::ofstream ofstr(path, std::ios::binary);
+  if (!ofstr.is_open()) return pmvs_io_fail(PMVS_EINVAL, "cannot write %s", path);
+  ofstr << "ply\nformat binary_little_endian 1.0\n";
+  for (int32_t t = 0; t < ntex; ++t) ofstr << "comment TextureFile " << tex_files[t] << "\n";
+  ofstr << "element vertex " << nv
+        << "\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\n"
+           "property float nz\nproperty uchar diffuse_red\nproperty uchar diffuse_green\nproperty uchar diffuse_blue\n"
+           "element face "
+        << nf << "\nproperty list uchar int vertex_indices\nproperty list uchar float texcoord\nproperty int texnumber\nend_header\n";
+  constexpr int64_t kChunk = 4096;  // records per write
+  std::vector<char> buf((size_t)(kChunk * 42));
+  auto put32 = [](char* dst, uint32_t u) {
+    for (int j = 0; j < 4; ++j) dst[j] = (char)((u >> (8 * j)) & 0xff);
+  };
+  auto putf = [&put32](char* dst, float f) {
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    put32(dst, u);
+  };
+  for (int64_t p0 = 0; p0 < nv; p0 += kChunk) {
+    const int64_t m = std::min<int64_t>(kChunk, nv - p0);
+    for (int64_t i = 0; i < m; ++i) {
+      char* rec = buf.data() + 27 * i;
+      for (int k = 0; k < 3; ++k) putf(rec + 4 * k, vertex[3 * (p0 + i) + k]), putf(rec + 12 + 4 * k, normal[3 * (p0 + i) + k]);
+      rec[24] = (char)color[3 * (p0 + i)], rec[25] = (char)color[3 * (p0 + i) + 1], rec[26] = (char)color[3 * (p0 + i) + 2];
+    }
+    ofstr.write(buf.data(), (std::streamsize)(27 * m));
+  }
+  for (int64_t p0 = 0; p0 < nf; p0 += kChunk) {
+    const int64_t m = std::min<int64_t>(kChunk, nf - p0);
+    for (int64_t i = 0; i < m; ++i) {
+      char* rec = buf.data() + 42 * i;
+      const int64_t f = p0 + i;
+      rec[0] = 3;
+      for (int k = 0; k < 3; ++k) put32(rec + 1 + 4 * k, (uint32_t)face[3 * f + k]);
+      rec[13] = 6;
+      const int32_t t = view[f];
+      for (int k = 0; k < 3; ++k) {
+        putf(rec + 14 + 8 * k, t < 0 ? 0.0f : pmvstex::tex_u(uv[6 * f + 2 * k], tex_dims[2 * t]));
+        putf(rec + 18 + 8 * k, t < 0 ? 0.0f : pmvstex::tex_v(uv[6 * f + 2 * k + 1], tex_dims[2 * t + 1]));
+      }
+      put32(rec + 38, (uint32_t)t);
+    }
+    ofstr.write(buf.data(), (std::streamsize)(42 * m));
   }
   return ofstr.good() ? PMVS_OK : pmvs_io_fail(PMVS_EINVAL, "write failed: %s", path);
 }

@@ -247,6 +247,30 @@ hipError_t brick_mesh_pass(const pmvs_volume& vol, int min_obs, long long nb, co
                            const unsigned char* obs, const unsigned char* color, long long vcap, long long fcap, const MeshArrays& out,
                            long long* nverts, long long* nfaces, hipStream_t st);
 
+// ---- the mesh rasterised into the targets and a view per face (pmvs_texmesh.hip; the definition is
+// csrc/pmvs_texmesh.h)
+// Device pointers of pmvs_raster_buffers / pmvs_texture_buffers (include/pmvs_amd.h); null = not wanted.
+struct RasterArrays {
+  int* face = nullptr;
+  float* depth = nullptr;
+};
+struct TextureArrays {
+  int* view = nullptr;
+  float *uv = nullptr, *score = nullptr;
+};
+// *ok = every one of the 3 * nf device face ids lies in [0, nv) (a kernel's one flag, read back).
+hipError_t mesh_ids_check(const int* face, long long nf, long long nv, bool* ok, hipStream_t st);
+// The nearest face and its depth per pixel of targets [first, first + count) (pixel offsets relative to
+// target `first`) of the device mesh, whose ids were checked.  Returns after the stream has finished the
+// work; its scratch (8 bytes per pixel of one group of at most eight targets, 8 bytes per (face, target of
+// the group) whose clipped box exceeds 64 pixels) is freed by then.
+hipError_t mesh_raster_pass(const DScene& s, const DView* hviews, int first, int count, const float* vertex, long long nf,
+                            const int* face, const RasterArrays& out, hipStream_t st);
+// The best target of the range per face, with the same raster rendered group by group inside the call; also
+// 8 bytes per face for the view and score the caller did not ask for.  nf < 1 writes nothing.
+hipError_t mesh_texture_pass(const DScene& s, const DView* hviews, int first, int count, const pmvs_texture_params& prm,
+                             const float* vertex, long long nf, const int* face, const TextureArrays& out, hipStream_t st);
+
 // ---- filter pass (pmvs_filter.hip)
 // The fields of a patch that neighbour and visibility tests read from OTHER patches (isNeighbor,
 // computeGain, isVisible), one 64-B line per patch instead of 2-3 lines of its 1.6-KB record;

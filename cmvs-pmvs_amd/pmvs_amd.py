@@ -153,6 +153,18 @@ class BrickBuffers(C.Structure):  # pmvs_brick_buffers
     _fields_ = [(k, C.c_void_p) for k in ("brick", "tsdf", "obs", "color")]
 
 
+class RasterBuffers(C.Structure):  # pmvs_raster_buffers
+    _fields_ = [(k, C.c_void_p) for k in ("face", "depth")]
+
+
+class TextureParams(C.Structure):  # pmvs_texture_params
+    _fields_ = [("depth_rel", C.c_float), ("min_area", C.c_float)]
+
+
+class TextureBuffers(C.Structure):  # pmvs_texture_buffers
+    _fields_ = [(k, C.c_void_p) for k in ("view", "uv", "score")]
+
+
 class SeedStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("trial", "pass_", "fail0", "fail1", "refined", "rounds", "candidates",
                                           "reserved")] + [(k, C.c_double) for k in ("wall_ms", "gen_ms", "refine_ms")]
@@ -203,6 +215,7 @@ EXPORTS = ["pmvs_last_error", "pmvs_device_count", "pmvs_scene_create", "pmvs_sc
            "pmvs_volume_from_points", "pmvs_write_ply_mesh_binary",
            "pmvs_loop_brick_tsdf", "pmvs_brick_tsdf_patches", "pmvs_brick_tsdf_mesh", "pmvs_loop_brick_mesh",
            "pmvs_brick_mesh_patches", "pmvs_brick_volume_from_points",
+           "pmvs_mesh_raster", "pmvs_mesh_texture", "pmvs_write_ply_texmesh_binary",
            "pmvs_loop_text", "pmvs_text_patches", "pmvs_selftest_format", "pmvs_selftest_labels",
            "pmvs_scene_set_shard", "pmvs_scene_set_shard_rccl", "pmvs_scene_set_cluster",
            "pmvs_scene_set_cluster_rccl", "pmvs_rccl_unique_id",
@@ -307,6 +320,13 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.pmvs_brick_mesh_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32] + brick_tail + mesh_tail
     lib.pmvs_brick_volume_from_points.argtypes = [C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Volume)]
     lib.pmvs_write_ply_mesh_binary.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    texmesh_tail = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]  # nv, vertex, nf, face
+    lib.pmvs_mesh_raster.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + texmesh_tail + [C.POINTER(RasterBuffers)]
+    lib.pmvs_mesh_texture.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(TextureParams)] + texmesh_tail + \
+                                     [C.POINTER(TextureBuffers)]
+    lib.pmvs_write_ply_texmesh_binary.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p),
+                                                  C.c_void_p]
     lib.pmvs_loop_text.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                    C.POINTER(C.c_int64)]
     lib.pmvs_text_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -1001,6 +1021,60 @@ class Scene:
         return self._mesh_call(lambda *a: self.lib.pmvs_brick_mesh_patches(self.handle, _ptr(pa), len(pa), *shared, min_obs, *a),
                                device, arrays)
 
+    # pmvs_raster_buffers: px pixels of the range; pmvs_texture_buffers: f faces
+    RASTER_ARRAYS = {"face": ("int32", ("px",)), "depth": ("float32", ("px",))}
+    TEXTURE_ARRAYS = {"view": ("int32", ("f",)), "uv": ("float32", ("f", 6)), "score": ("float32", ("f",))}
+
+    def _mesh_inputs(self, vertex, face, device):
+        """(nv, vertex pointer, nf, face pointer) of a mesh and the arrays that keep the pointers alive: numpy
+        in host mode, torch tensors on the scene's device in device mode (device tensors are taken as they are)."""
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            v = torch.as_tensor(vertex, dtype=torch.float32, device=dev).contiguous().reshape(-1, 3)
+            f = torch.as_tensor(face, dtype=torch.int32, device=dev).contiguous().reshape(-1, 3)
+            ptrs = [a.data_ptr() if a.numel() else None for a in (v, f)]
+        else:
+            if hasattr(vertex, "cpu"):
+                vertex, face = vertex.cpu().numpy(), face.cpu().numpy()
+            v = np.ascontiguousarray(vertex, np.float32).reshape(-1, 3)
+            f = np.ascontiguousarray(face, np.int32).reshape(-1, 3)
+            ptrs = [_ptr(a) if a.size else None for a in (v, f)]
+        return (len(v), ptrs[0], len(f), ptrs[1]), (v, f)
+
+    def mesh_raster(self, vertex, face, device: bool = False, arrays=None, first_target: int = 0, num_targets=None) -> dict:
+        """pmvs_mesh_raster: the mesh (vertex [nv, 3] float32, face [nf, 3] int32 vertex ids) rasterised into
+        targets [first_target, first_target + num_targets) (None: all from first_target on) at the scene's
+        level, keyed by the fields of pmvs_raster_buffers: face [pixels] int32 (the nearest face, -1 = empty)
+        and depth [pixels] float32 (its depth, 0 = empty); pixel_map_layout() of the same range gives each
+        target's pixels.  Needs no loop result.  device=True: the mesh and the maps are torch tensors on the
+        scene's device.  arrays: the names wanted (None = all)."""
+        num, _ = self._range(first_target, num_targets)
+        mesh, keep = self._mesh_inputs(vertex, face, device)
+        out, buf = self._new_arrays(RasterBuffers, self.RASTER_ARRAYS, arrays, device,
+                                    px=int(self.pixel_map_layout(first_target, num)[1][-1]))
+        _check(self.lib.pmvs_mesh_raster(self.handle, self._flags(False, device), first_target, num, *mesh, C.byref(buf)))
+        del keep
+        return out
+
+    def mesh_texture(self, vertex, face, depth_rel: float = 0.01, min_area: float = 0.0, device: bool = False, arrays=None,
+                     first_target: int = 0, num_targets=None) -> dict:
+        """pmvs_mesh_texture: per face of the mesh the target of the range that sees it best -- front-facing,
+        its three corners inside the image and not more than depth_rel of their depth behind the mesh's own
+        raster, with the largest projected area, at least min_area pixels^2 -- keyed by the fields of
+        pmvs_texture_buffers: view [nf] int32 (a scene target index, -1 = none), uv [nf, 6] float32 (the
+        corners' (x, y) in level-0 pixels of that target, 0 without one) and score [nf] float32 (the area).
+        Needs no loop result.  device=True: the mesh and the arrays are torch tensors on the scene's device.
+        arrays: the names wanted (None = all)."""
+        num, _ = self._range(first_target, num_targets)
+        mesh, keep = self._mesh_inputs(vertex, face, device)
+        out, buf = self._new_arrays(TextureBuffers, self.TEXTURE_ARRAYS, arrays, device, f=mesh[2])
+        prm = TextureParams(depth_rel, min_area)
+        _check(self.lib.pmvs_mesh_texture(self.handle, self._flags(False, device), first_target, num, C.byref(prm), *mesh,
+                                          C.byref(buf)))
+        del keep
+        return out
+
     def _text(self, call, writer_order, index2image, device: bool, out):
         """call(flags, index2image, out, cap, byref(size)): a size query, the buffer (numpy uint8, or a torch
         uint8 tensor on the scene's device; `out` supplies it) and the call that fills it; returns the
@@ -1257,6 +1331,26 @@ def write_ply_mesh_binary(path: str, vertex, normal, color, face):
     if not len(v) == len(nm) == len(col):
         raise ValueError("write_ply_mesh_binary takes vertex arrays of one length")
     _check(load_library().pmvs_write_ply_mesh_binary(path.encode(), len(v), _ptr(v), _ptr(nm), _ptr(col), len(f), _ptr(f)))
+
+
+def write_ply_texmesh_binary(path: str, vertex, normal, color, face, view, uv, tex_files, tex_dims):
+    """pmvs_write_ply_texmesh_binary: a mesh with Scene.mesh_texture's view [nf] and uv [nf, 6] as one binary
+    little-endian PLY of 27-byte vertices and 42-byte faces (ids, texcoord, texnumber), one `comment
+    TextureFile` line per name of tex_files; tex_dims [ntex, 2] = the (width, height) of each texture, which
+    scale the level-0 pixel uv to [0, 1] with V up."""
+    v = np.ascontiguousarray(vertex, np.float32).reshape(-1, 3)
+    nm = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+    col = np.ascontiguousarray(color, np.uint8).reshape(-1, 3)
+    f = np.ascontiguousarray(face, np.int32).reshape(-1, 3)
+    vw = np.ascontiguousarray(view, np.int32).reshape(-1)
+    tc = np.ascontiguousarray(uv, np.float32).reshape(-1, 6)
+    dims = np.ascontiguousarray(tex_dims, np.int32).reshape(-1, 2)
+    if not len(v) == len(nm) == len(col) or not len(f) == len(vw) == len(tc) or len(dims) != len(tex_files):
+        raise ValueError("write_ply_texmesh_binary takes vertex arrays of one length, face arrays of one length and one "
+                         "(width, height) per texture file")
+    names = (C.c_char_p * max(len(tex_files), 1))(*[os.fsencode(n) for n in tex_files])
+    _check(load_library().pmvs_write_ply_texmesh_binary(path.encode(), len(v), _ptr(v), _ptr(nm), _ptr(col), len(f), _ptr(f),
+                                                        _ptr(vw), _ptr(tc), len(tex_files), names, _ptr(dims)))
 
 
 def write_pfm(path: str, data):

@@ -750,6 +750,104 @@ pmvs_status pmvs_brick_mesh_patches(pmvs_scene* scene, const pmvs_patch* patches
  * brick grid past 2^31-1 is PMVS_EINVAL): the volume `pmvs2 ... FINEMESH` uses. */
 pmvs_status pmvs_brick_volume_from_points(int64_t n, const float* coord, int32_t cells, int32_t pad, pmvs_volume* volume);
 
+/* TEXTURING without an atlas: the textures are the target images themselves.  A triangle mesh (vertex nv x 3
+ * f32, face nf x 3 int32 vertex ids; from pmvs_tsdf_mesh, pmvs_brick_tsdf_mesh or the caller's own) is
+ * rasterised into the targets [first_target, first_target + num_targets) at the scene's level L, and every
+ * face gets the target that sees it best and unoccluded and its corners' positions in that image.  Only the
+ * device, the stream and the views are taken from the scene; no loop result is needed.  There is no
+ * reference for this; csrc/pmvs_texmesh.h implements what follows once, for host and device.  All f64
+ * arithmetic is unfused, from the f32 inputs, sums left to right in the order written.
+ *
+ * Per vertex i and target t (W x H its image at level L): (x_i, y_i) = CCamera::project(view t, (V_i, 1.0f), L)
+ * and z_i = OpticalAxis(t) . (V_i, 1.0f), all f32.
+ *
+ * A. THE RASTER (pmvs_mesh_raster): per pixel of every target of the range, the nearest face and its depth.
+ *  1. Face f = (i0, i1, i2) is DRAWN in t iff the three z are finite and > 0, the six coordinates are finite,
+ *     and A = (x1-x0)*(y2-y0) - (y1-y0)*(x2-x0) (differences and products in f64) is finite and != 0.  Both
+ *     windings are drawn: a back face occludes too.
+ *  2. Its box: u0 = max(0, ceil(min x)), u1 = min(W-1, floor(max x)), v0 and v1 likewise from y and H, in
+ *     double (project's clamped +-2^31 cannot wrap).  An empty box draws nothing.
+ *  3. Integer pixel (u, v) of the box is covered iff, with
+ *       w0 = (x2-x1)*(v-y1) - (y2-y1)*(u-x1), w1 = (x0-x2)*(v-y2) - (y0-y2)*(u-x2),
+ *       w2 = (x1-x0)*(v-y0) - (y1-y0)*(u-x0),
+ *     all wk >= 0 when A > 0, all wk <= 0 when A < 0.  A shared edge is covered from both sides; step 5 makes
+ *     that harmless, and no fill rule is needed.
+ *  4. Its depth there: lk = wk / A, inv = l0/(double)z0 + l1/(double)z1 + l2/(double)z2, d = (float)(1.0 / inv)
+ *     (1/z is affine in the image: the optical axis is the projection's third row scaled).  The pixel takes
+ *     the face iff d is finite and > 0.
+ *  5. A pixel keeps the minimum key (depth_bits(d) << 32) | f: the smallest depth and, at equal depths, the
+ *     lower face id -- the maps' rule, so nothing depends on the order of the work.
+ *  6. face: int32 per pixel, -1 where empty; depth: f32 per pixel, +0.0 where empty; laid out as
+ *     pmvs_pixel_map_layout gives for the range.  Either pointer may be NULL.  nf = 0: every pixel is empty.
+ *
+ * B. VIEW SELECTION (pmvs_mesh_texture).  Face f is ELIGIBLE in target t of the range iff
+ *  1. it is drawn in t (A.1);
+ *  2. it is seen from its front: N = (V1-V0) x (V2-V0) in f64 and N . (centre(t) - V0) > 0 (the extraction
+ *     winds faces outward);
+ *  3. every corner k is visible: the pixel q = (floor((double)xk + 0.5), floor((double)yk + 0.5)) lies in the
+ *     image (the fusion's pixel_at), and with (fq, dq) the raster of A at q either fq == -1 (an empty pixel
+ *     occludes nothing) or (double)zk - (double)dq <= (double)depth_rel * (double)zk.  All three corners
+ *     inside the image puts the whole face inside;
+ *  4. its score s = (float)(0.5 * fabs(A)), the projected area in pixels^2, is >= min_area.
+ *  view(f) = the eligible t with the greatest s, the lowest t on ties, as a scene target index; -1 if none.
+ *  score(f) = the winner's s, 0 with view -1.  uv(f) = six f32, (x, y) of the three corners from
+ *  project(view, (Vk, 1.0f), 0): LEVEL-0 pixels, so they address the image file whatever the scene's level;
+ *  0 with view -1.  Any pointer may be NULL.  nf = 0 writes nothing.
+ *  The raster B reads is A's, rendered inside the call by the same code.
+ *
+ * C. THE FILE (pmvs_write_ply_texmesh_binary; host arrays).  The header is exactly
+ *     ply\nformat binary_little_endian 1.0\n
+ *     comment TextureFile <tex_files[0]>\n ... comment TextureFile <tex_files[ntex-1]>\n
+ *     element vertex <nv>\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\n
+ *     property float ny\nproperty float nz\nproperty uchar diffuse_red\nproperty uchar diffuse_green\n
+ *     property uchar diffuse_blue\nelement face <nf>\nproperty list uchar int vertex_indices\n
+ *     property list uchar float texcoord\nproperty int texnumber\nend_header\n
+ *  then nv 27-byte vertex records as pmvs_write_ply_mesh_binary writes them and nf 42-byte face records: the
+ *  count 3 and three ids (13 bytes), the count 6 and u0 v0 u1 v1 u2 v2 (25 bytes), texnumber = view (4 bytes).
+ *  With (W0, H0) = tex_dims[2 * view], tex_dims[2 * view + 1] and (x, y) a corner's uv:
+ *  u = (float)clamp(((double)x + 0.5) / W0, 0, 1), v = (float)clamp(1.0 - ((double)y + 0.5) / H0, 0, 1): pixel
+ *  centres at integers, the V axis up.  A face with view -1 gets six zeros.
+ *
+ * flags: only PMVS_EXPORT_DEVICE; with it every array pointer (vertex, face and the buffers') is a device
+ * pointer on the scene's device.  PMVS_EINVAL: a NULL scene, params or buffers; another flag bit; an empty
+ * range or one outside the scene's targets; nv or nf negative or above 2^31-1; a NULL array with a positive
+ * count; depth_rel or min_area not finite or < 0; a face id outside [0, nv) (host ids are checked before the
+ * scene is touched, device ids by a kernel whose one flag is read back before any id is used as an index);
+ * the writer: a NULL path, a view outside -1..ntex-1, a texture dim < 1, a NULL name, a file that cannot be
+ * written.  PMVS_ENOMEM when the device cannot hold the scratch: 8 bytes per pixel of one group of at most
+ * eight targets (the keys); nothing per vertex; per face 8 bytes for each (face, target of the group) whose
+ * clipped box exceeds 64 pixels (at most 64 bytes per face, none for a mesh at image resolution) and, in
+ * pmvs_mesh_texture, 8 bytes for the running view and score where the caller did not ask for them; in host
+ * mode also the mesh (12 bytes per vertex and per face) and the requested outputs (8 bytes per pixel of the
+ * range; 32 bytes per face).  All of it is allocated for the call and freed on return; the calls return after
+ * their work has finished. */
+typedef struct pmvs_raster_buffers {  /* either pointer may be NULL: that array is skipped */
+  int32_t* face;   /* pixels of the range: the nearest face, -1 = empty */
+  float*   depth;  /* pixels of the range: its depth, +0.0 = empty */
+} pmvs_raster_buffers;
+
+typedef struct pmvs_texture_params {
+  float depth_rel;  /* finite, >= 0: a corner may lie this fraction of its depth behind the raster */
+  float min_area;   /* finite, >= 0: the smallest projected area, in pixels^2 at the scene's level */
+} pmvs_texture_params;
+
+typedef struct pmvs_texture_buffers {  /* any pointer may be NULL: that array is skipped */
+  int32_t* view;   /* nf: the chosen target, -1 = none */
+  float*   uv;     /* nf x 6: the corners in level-0 pixels of that target */
+  float*   score;  /* nf: the winner's projected area */
+} pmvs_texture_buffers;
+
+pmvs_status pmvs_mesh_raster(pmvs_scene* scene, int32_t flags, int32_t first_target, int32_t num_targets, int64_t nv,
+                             const float* vertex, int64_t nf, const int32_t* face, const pmvs_raster_buffers* buffers);
+pmvs_status pmvs_mesh_texture(pmvs_scene* scene, int32_t flags, int32_t first_target, int32_t num_targets,
+                              const pmvs_texture_params* params, int64_t nv, const float* vertex, int64_t nf,
+                              const int32_t* face, const pmvs_texture_buffers* buffers);
+/* tex_files: ntex names, written as given; tex_dims: ntex x 2, the (width, height) the uv are scaled by. */
+pmvs_status pmvs_write_ply_texmesh_binary(const char* path, int64_t nv, const float* vertex, const float* normal,
+                                          const uint8_t* color, int64_t nf, const int32_t* face, const int32_t* view,
+                                          const float* uv, int32_t ntex, const char* const* tex_files,
+                                          const int32_t* tex_dims);
+
 /* The .ply / .patch / .pset text of the model, formatted on the device: the bytes pmvs_write_ply /
  * pmvs_write_patches / pmvs_write_pset write from the export of the same records and flags
  * (CPatchOrganizerS::writePLY patchOrganizerS.cpp:687-776, writePatches2 :89-132 with Patch::operator<<
