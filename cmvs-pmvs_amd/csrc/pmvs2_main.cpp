@@ -128,7 +128,7 @@ void usage(const char* argv0) {
             << "oimages  5  0 2 4 6 8 (enumeration)" << std::endl
             << "        -1  24 48 (range specification)" << std::endl
             << std::endl
-            << "[Optional export] PATCH PSET DEPTH PIXDEPTH FUSE MESH FINEMESH TEXMESH" << std::endl
+            << "[Optional export] PATCH PSET DEPTH PIXDEPTH FUSE MESH FINEMESH TEXMESH ATLAS" << std::endl
             << " i.e export patch and pset: prefix option_file PATCH PSET"
             << " i.e export patch only: prefix option_file PATCH" << std::endl
             << " DEPTH: every target image's depth map, one value per csize x csize cell, as" << std::endl
@@ -152,7 +152,12 @@ void usage(const char* argv0) {
             << "        that sees it from the front with the largest projected area and whose view of its three corners" << std::endl
             << "        the mesh itself does not block (within 1 % of the depth), as the binary PLY" << std::endl
             << "        models/option_file.texmesh.ply with one `comment TextureFile ../visualize/<image>` per target" << std::endl
-            << "        image, per-face texcoord (u, v in [0, 1], v up) and texnumber (-1 = no image sees the face)" << std::endl;
+            << "        image, per-face texcoord (u, v in [0, 1], v up) and texnumber (-1 = no image sees the face)" << std::endl
+            << " ATLAS: TEXMESH's mesh and views baked into one texture: every face's texels cut out of its image and" << std::endl
+            << "        packed as right triangles of side 1 .. 64 texels (one texel per level-0 pixel of the face's" << std::endl
+            << "        longest edge) into an atlas 8192 texels wide, as the binary PPM models/option_file.atlas.ppm and" << std::endl
+            << "        the binary PLY models/option_file.atlas.ply with the single `comment TextureFile" << std::endl
+            << "        option_file.atlas.ppm` (texnumber 0, or -1 for a face without texels)" << std::endl;
 }
 
 }  // namespace
@@ -166,7 +171,7 @@ int main(int argc, char* argv[]) {
   std::cout << std::endl;
   const std::string prefix = argv[1], option = argv[2];
   bool export_patch = false, export_pset = false, export_depth = false, export_pixdepth = false, export_fuse = false, export_mesh = false,
-       export_finemesh = false, export_texmesh = false;
+       export_finemesh = false, export_texmesh = false, export_atlas = false;
   for (int i = 3; i < argc; ++i) {
     if (std::string(argv[i]) == "PATCH") export_patch = true;
     if (std::string(argv[i]) == "PSET") export_pset = true;
@@ -176,6 +181,7 @@ int main(int argc, char* argv[]) {
     if (std::string(argv[i]) == "MESH") export_mesh = true;
     if (std::string(argv[i]) == "FINEMESH") export_finemesh = true;
     if (std::string(argv[i]) == "TEXMESH") export_texmesh = true;
+    if (std::string(argv[i]) == "ATLAS") export_atlas = true;
   }
   const double t0 = now_s();
 
@@ -480,7 +486,7 @@ int main(int argc, char* argv[]) {
       CHECK("pfm", pmvs_write_pfm((out + name).c_str(), dims[0], dims[1], depth.data()));
     }
   }
-  if (export_fuse || export_mesh || export_finemesh || export_texmesh) {
+  if (export_fuse || export_mesh || export_finemesh || export_texmesh || export_atlas) {
     // the model just written fused over all target images (pmvs_loop_fuse, writer order): a counting
     // call sizes the host arrays
     pmvs_fuse_params fp{};
@@ -554,13 +560,21 @@ int main(int argc, char* argv[]) {
       CHECK("fine mesh ply", pmvs_write_ply_mesh_binary((out + ".finemesh.ply").c_str(), nv, vertex.data(), vnormal.data(),
                                                         vcolor.data(), nf, face.data()));
     }
-    if (export_texmesh) {
+    if (export_texmesh || export_atlas) {
       // MESH's mesh (the same volume and parameters) obtained in device mode and kept there, a target chosen
-      // per face over all target images (pmvs_mesh_texture), then one fetch and one write
+      // per face over all target images (pmvs_mesh_texture), then one fetch and one write.  ATLAS bakes the
+      // same device arrays into one image (pmvs_mesh_atlas: a sizing call, then the render) before they are freed.
       int64_t nv = 0, nf = 0;
       std::vector<float> vertex, vnormal, uv;
       std::vector<uint8_t> vcolor;
       std::vector<int32_t> face, view;
+      std::vector<float> atlas_uv;  // ATLAS: the atlas, its corners and which faces have texels
+      std::vector<int32_t> atlas_view;
+      std::vector<uint8_t> atlas_rgb;
+      pmvs_atlas_params ap{};
+      ap.width = 8192, ap.max_side = 64, ap.scale = 1.0f;
+      pmvs_atlas_layout al{};
+      al.width = ap.width;
       pmvs_volume vol{};
       if (npts > 0 && pmvs_volume_from_points(npts, coord.data(), 256, 3, &vol) == PMVS_OK) {
         const int32_t flags = PMVS_EXPORT_WRITER_ORDER | PMVS_EXPORT_DEVICE;
@@ -594,6 +608,27 @@ int main(int argc, char* argv[]) {
           std::cerr << "pmvs2: textured mesh: the fetch failed" << std::endl;
           return 1;
         }
+        if (export_atlas) {
+          CHECK("atlas", pmvs_mesh_atlas(sc, PMVS_EXPORT_DEVICE, &ap, nv, mb.vertex, nf, mb.face, tb.view, 0, nullptr, &al));
+          const size_t nfa = (size_t)std::max<int64_t>(nf, 1), texels = (size_t)al.height * (size_t)al.width;
+          const size_t a_view = nfa * 6 * 4, a_rgb = a_view + nfa * 4, abytes = a_rgb + std::max<size_t>(texels * 3, 1);
+          char* ablock = nullptr;  // uv (float), atlas_view (int32), rgb (bytes)
+          if (hipMalloc((void**)&ablock, abytes) != hipSuccess) {
+            std::cerr << "pmvs2: atlas: " << abytes << " bytes of device memory" << std::endl;
+            return 1;
+          }
+          pmvs_atlas_buffers ab{};
+          ab.uv = (float*)ablock, ab.atlas_view = (int32_t*)(ablock + a_view), ab.rgb = (uint8_t*)(ablock + a_rgb);
+          CHECK("atlas", pmvs_mesh_atlas(sc, PMVS_EXPORT_DEVICE, &ap, nv, mb.vertex, nf, mb.face, tb.view, al.height, &ab, &al));
+          atlas_uv.resize((size_t)nf * 6), atlas_view.resize((size_t)nf), atlas_rgb.resize(texels * 3);
+          if ((nf && (hipMemcpy(atlas_uv.data(), ab.uv, atlas_uv.size() * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                      hipMemcpy(atlas_view.data(), ab.atlas_view, atlas_view.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)) ||
+              (texels && hipMemcpy(atlas_rgb.data(), ab.rgb, atlas_rgb.size(), hipMemcpyDeviceToHost) != hipSuccess)) {
+            std::cerr << "pmvs2: atlas: the fetch failed" << std::endl;
+            return 1;
+          }
+          (void)hipFree(ablock);
+        }
         (void)hipFree(block);
         vertex.resize((size_t)nv * 3), vnormal.resize((size_t)nv * 3), vcolor.resize((size_t)nv * 3);
         face.resize((size_t)nf * 3), view.resize((size_t)nf), uv.resize((size_t)nf * 6);
@@ -606,9 +641,22 @@ int main(int argc, char* argv[]) {
       }
       std::vector<const char*> names((size_t)tnum);
       for (int t = 0; t < tnum; ++t) names[t] = tex_names[t].c_str();
-      CHECK("textured mesh ply",
-            pmvs_write_ply_texmesh_binary((out + ".texmesh.ply").c_str(), nv, vertex.data(), vnormal.data(), vcolor.data(), nf, face.data(),
-                                          view.data(), uv.data(), tnum, names.data(), tex_dims.data()));
+      if (export_texmesh)
+        CHECK("textured mesh ply",
+              pmvs_write_ply_texmesh_binary((out + ".texmesh.ply").c_str(), nv, vertex.data(), vnormal.data(), vcolor.data(), nf,
+                                            face.data(), view.data(), uv.data(), tnum, names.data(), tex_dims.data()));
+      if (export_atlas) {
+        // an empty atlas (no face has texels) is written as one black texel, which no face refers to
+        const std::string ppm = option + ".atlas.ppm";
+        int32_t adims[2] = {(int32_t)al.width, (int32_t)al.height};
+        if (al.height == 0) adims[0] = adims[1] = 1, atlas_rgb.assign(3, 0);
+        atlas_view.resize((size_t)nf, -1), atlas_uv.resize((size_t)nf * 6, 0.0f);
+        CHECK("atlas ppm", pmvs_write_ppm((prefix + "models/" + ppm).c_str(), adims[0], adims[1], atlas_rgb.data()));
+        const char* aname = ppm.c_str();
+        CHECK("atlas ply",
+              pmvs_write_ply_texmesh_binary((out + ".atlas.ply").c_str(), nv, vertex.data(), vnormal.data(), vcolor.data(), nf,
+                                            face.data(), atlas_view.data(), atlas_uv.data(), 1, &aname, adims));
+      }
     }
   }
   pmvs_scene_destroy(sc);

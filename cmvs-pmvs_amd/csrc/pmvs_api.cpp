@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/pmvs_amd.h"
+#include "pmvs_atlas.h"
 #include "pmvs_brick.h"
 #include "pmvs_features.h"
 #include "pmvs_fmt.h"
@@ -2206,6 +2207,92 @@ pmvs_status pmvs_mesh_texture(pmvs_scene* sc, int32_t flags, int32_t first_targe
   EXPCHK(stg.fixed(&a.score, buffers->score, (size_t)nf));
   EXPCHK(mesh_texture_pass(sc->ds, sc->hviews.data(), first_target, num_targets, *params, d_vertex, nf, d_face, a, sc->stream));
   EXPCHK(stg.finish(sc->stream, true));
+  return PMVS_OK;
+}
+
+// ---- the textured mesh baked into one atlas image (pmvs_atlas.hip)
+namespace {
+bool atlas_params_ok(const pmvs_atlas_params* p) {
+  return p && p->max_side >= 1 && p->max_side <= PMVS_ATLAS_MAX_SIDE && p->width >= p->max_side + 5 &&
+         p->width <= PMVS_ATLAS_MAX_WIDTH && std::isfinite(p->scale) && p->scale > 0.0f;
+}
+
+enum { kAtlasRows = 1 };  // Staging part: the two images share the written rows
+}  // namespace
+
+pmvs_status pmvs_atlas_layout_from_counts(const pmvs_atlas_params* params, const int64_t* counts, pmvs_atlas_layout* layout,
+                                          int64_t* band_y) {
+  if (!atlas_params_ok(params) || !counts || !layout) return fail(PMVS_EINVAL, "invalid argument");
+  for (int n = 1; n <= params->max_side; ++n)
+    if (counts[n] < 0) return fail(PMVS_EINVAL, "atlas_layout_from_counts: class %d has a negative count", n);
+  // 251 classes of up to 2^63 faces: summed in 128 bits and reported saturated, so that nothing wraps
+  __int128 y = 0, placed = 0, cells = 0;
+  const auto sat = [](__int128 v) { return v > INT64_MAX ? INT64_MAX : (int64_t)v; };
+  for (int n = params->max_side; n >= 1; --n) {
+    if (band_y) band_y[n] = sat(y);
+    y += (__int128)pmvsatlas::class_rows(counts[n], params->width, n) * (n + 5);
+    placed += counts[n];
+    cells += pmvsatlas::class_slots(counts[n]);
+  }
+  if (band_y) band_y[0] = sat(y);
+  *layout = pmvs_atlas_layout{params->width, sat(y), sat(placed), sat(cells)};
+  if (y > INT32_MAX) return fail(PMVS_EUNSUPPORTED, "atlas_layout_from_counts: the atlas height %lld exceeds 2^31-1", (long long)sat(y));
+  return PMVS_OK;
+}
+
+pmvs_status pmvs_mesh_atlas(pmvs_scene* sc, int32_t flags, const pmvs_atlas_params* params, int64_t nv, const float* vertex,
+                            int64_t nf, const int32_t* face, const int32_t* view, int64_t height_cap,
+                            const pmvs_atlas_buffers* buffers, pmvs_atlas_layout* layout) {
+  if (!atlas_params_ok(params) || !layout || !flags_ok(flags, PMVS_EXPORT_DEVICE) || nv < 0 || nv > INT32_MAX || nf < 0 ||
+      nf > INT32_MAX || (nv > 0 && !vertex) || (nf > 0 && (!face || !view)) || height_cap < 0 || !sc)
+    return fail(PMVS_EINVAL, "invalid argument");
+  const bool dev = (flags & PMVS_EXPORT_DEVICE) != 0;
+  const int tnum = sc->ds.tnum;
+  for (int t = 0; t < tnum; ++t)
+    if (sc->hviews[t].w[0] < 2 || sc->hviews[t].h[0] < 2)
+      return fail(PMVS_EINVAL, "mesh_atlas: target %d is smaller than 2 x 2 pixels at level 0", t);
+  if (!dev)
+    for (int64_t f = 0; f < nf; ++f)
+      if (view[f] < -1 || view[f] >= tnum) return fail(PMVS_EINVAL, "mesh_atlas: face %lld has a view outside [-1, num_targets)", (long long)f);
+  const pmvs_atlas_buffers none{};
+  const pmvs_atlas_buffers& b = buffers ? *buffers : none;
+  CallArena arena;
+  const float* d_vertex = nullptr;
+  const int* d_face = nullptr;
+  const int* d_view = view;
+  if (!dev) {  // the host ids are checked, then the mesh goes up
+    if (pmvs_status st = texmesh_device_mesh(sc, false, "mesh_atlas", nv, vertex, nf, face, arena, &d_vertex, &d_face)) return st;
+    int* uview = nullptr;
+    EXPCHK(arena.alloc(&uview, (size_t)nf));
+    if (nf) EXPCHK(hipMemcpyAsync(uview, view, (size_t)nf * sizeof(int), hipMemcpyHostToDevice, sc->stream));
+    d_view = uview;
+  } else {
+    HIPCHK(hipSetDevice(sc->device));
+    d_vertex = vertex, d_face = face;
+    bool ids_ok = true;
+    EXPCHK(atlas_ids_check(face, view, nf, nv, tnum, &ids_ok, sc->stream));
+    if (!ids_ok) return fail(PMVS_EINVAL, "mesh_atlas: a face has a vertex id outside [0, nv) or a view outside [-1, num_targets)");
+  }
+  AtlasWork work;
+  long long counts[PMVS_ATLAS_MAX_SIDE + 1];
+  EXPCHK(atlas_classify(sc->ds, *params, d_vertex, nf, d_face, d_view, work, counts, sc->stream));
+  int64_t counts64[PMVS_ATLAS_MAX_SIDE + 1], band_y[PMVS_ATLAS_MAX_SIDE + 1];
+  for (int n = 0; n <= PMVS_ATLAS_MAX_SIDE; ++n) counts64[n] = counts[n];
+  if (pmvs_status st = pmvs_atlas_layout_from_counts(params, counts64, layout, band_y)) {
+    if (!dev) EXPCHK(hipStreamSynchronize(sc->stream));  // the uploads' arena is freed on return
+    return st;
+  }
+  const size_t rows = (size_t)std::min<int64_t>(layout->height, height_cap), W = (size_t)params->width;
+  Staging stg(arena, dev);
+  AtlasArrays a;
+  EXPCHK(stg.capped(&a.rgb, b.rgb, rows, W * 3, kAtlasRows));
+  EXPCHK(stg.capped(&a.texel_face, b.texel_face, rows, W, kAtlasRows));
+  EXPCHK(stg.fixed(&a.uv, b.uv, (size_t)nf * 6));
+  EXPCHK(stg.fixed(&a.atlas_view, b.atlas_view, (size_t)nf));
+  long long band_ll[PMVS_ATLAS_MAX_SIDE + 1];
+  for (int n = 0; n <= PMVS_ATLAS_MAX_SIDE; ++n) band_ll[n] = n <= params->max_side ? band_y[n] : 0;
+  EXPCHK(atlas_render_pass(sc->ds, *params, d_vertex, nf, d_face, d_view, work, counts, band_ll, (long long)rows, a, sc->stream));
+  EXPCHK(stg.finish(sc->stream, true));  // in device mode too: the uploads' arena is freed on return
   return PMVS_OK;
 }
 

@@ -173,6 +173,20 @@ __device__ __forceinline__ int get_mask(const DScene& s, const DView& v, const f
   return s.masks[v.mask_off[level] + (long long)iy * v.w[level] + ix];
 }
 
+// A caller's triangle mesh (pmvs_texmesh.hip, pmvs_atlas.hip); every face id lies in [0, nv): checked before
+// the first launch that gathers through one.
+struct MeshView {
+  const float* __restrict__ vertex;
+  const int* __restrict__ face;
+  int nf;
+};
+__device__ __forceinline__ void load_face(const MeshView& m, int f, float V[3][4]) {
+  for (int k = 0; k < 3; ++k) {
+    const long long i = m.face[3 * (long long)f + k];
+    V[k][0] = m.vertex[3 * i], V[k][1] = m.vertex[3 * i + 1], V[k][2] = m.vertex[3 * i + 2], V[k][3] = 1.0f;
+  }
+}
+
 __device__ __forceinline__ float robustincc(float rhs) { return __fdiv_rn(rhs, 1.0f + 3.0f * rhs); }
 __device__ __forceinline__ float unrobustincc(float rhs) { return __fdiv_rn(rhs, 1.0f - 3.0f * rhs); }
 

@@ -677,6 +677,17 @@ pmvs_status pmvs_write_pfm(const char* path, int32_t width, int32_t height, cons
   return ofstr.good() ? PMVS_OK : pmvs_io_fail(PMVS_EINVAL, "write failed: %s", path);
 }
 
+// A binary P6 image, top row first (the atlas): pmvs_ppm_load's inverse.
+pmvs_status pmvs_write_ppm(const char* path, int32_t width, int32_t height, const uint8_t* rgb) {
+  if (!path || !rgb || width <= 0 || height <= 0) return pmvs_io_fail(PMVS_EINVAL, "invalid argument");
+  std::ofstream ofstr(path, std::ios::binary);
+  if (!ofstr.is_open()) return pmvs_io_fail(PMVS_EINVAL, "cannot write %s", path);
+  ofstr << "P6\n" << width << ' ' << height << "\n255\n";
+  const size_t row = (size_t)width * 3;
+  for (int y = 0; y < height; ++y) ofstr.write(reinterpret_cast<const char*>(rgb) + (size_t)y * row, (std::streamsize)row);
+  return ofstr.good() ? PMVS_OK : pmvs_io_fail(PMVS_EINVAL, "write failed: %s", path);
+}
+
 // A fused point cloud (pmvs_loop_fuse) as binary little-endian PLY: 28-byte records.
 pmvs_status pmvs_write_ply_binary(const char* path, int64_t n, const float* coord, const float* normal,
                                   const uint8_t* color, const uint8_t* support) {

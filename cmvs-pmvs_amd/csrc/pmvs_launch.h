@@ -271,6 +271,34 @@ hipError_t mesh_raster_pass(const DScene& s, const DView* hviews, int first, int
 hipError_t mesh_texture_pass(const DScene& s, const DView* hviews, int first, int count, const pmvs_texture_params& prm,
                              const float* vertex, long long nf, const int* face, const TextureArrays& out, hipStream_t st);
 
+// ---- the textured mesh baked into one atlas image (pmvs_atlas.hip; the definition is csrc/pmvs_atlas.h)
+// Device pointers of pmvs_atlas_buffers (include/pmvs_amd.h); null = not wanted.
+struct AtlasArrays {
+  unsigned char* rgb = nullptr;
+  int* texel_face = nullptr;
+  float* uv = nullptr;
+  int* atlas_view = nullptr;
+};
+// *ok = every one of the 3 * nf device face ids lies in [0, nv) and every one of the nf device views in
+// [-1, tnum) (a kernel's one flag, read back).
+hipError_t atlas_ids_check(const int* face, const int* view, long long nf, long long nv, int tnum, bool* ok, hipStream_t st);
+// The classes of a call's faces, between its two steps; owns the per-face scratch (10 bytes per face and
+// the sort's temporary storage).
+struct AtlasWork {
+  DevBuf<unsigned char> cls, cls_sorted;
+  DevBuf<int> ids, order;
+};
+// Step 1-2: the class byte of every face (0 = not placed) and the faces per class in counts[0, 252).
+// Returns after the stream has finished the work.
+hipError_t atlas_classify(const DScene& s, const pmvs_atlas_params& prm, const float* vertex, long long nf, const int* face,
+                          const int* view, AtlasWork& w, long long* counts, hipStream_t st);
+// Steps 3-7 for the layout those counts give (band_y[n] = the first row of class n, H = the atlas height):
+// uv and atlas_view of every face and the first `rows` rows of the two images.  Returns after the stream
+// has finished the work.
+hipError_t atlas_render_pass(const DScene& s, const pmvs_atlas_params& prm, const float* vertex, long long nf, const int* face,
+                             const int* view, AtlasWork& w, const long long* counts, const long long* band_y, long long rows,
+                             const AtlasArrays& out, hipStream_t st);
+
 // ---- filter pass (pmvs_filter.hip)
 // The fields of a patch that neighbour and visibility tests read from OTHER patches (isNeighbor,
 // computeGain, isVisible), one 64-B line per patch instead of 2-3 lines of its 1.6-KB record;

@@ -55,18 +55,6 @@ struct TexGroup {                  // one group of targets, by value to the kern
   long long off[kGroupTargets];    // first pixel of each target's map in the group's keys
 };
 
-struct MeshView {  // the caller's mesh; every face id lies in [0, nv): checked before the first launch
-  const float* __restrict__ vertex;
-  const int* __restrict__ face;
-  int nf;
-};
-
-__device__ __forceinline__ void load_face(const MeshView& m, int f, float V[3][4]) {
-  for (int k = 0; k < 3; ++k) {
-    const long long i = m.face[3 * (long long)f + k];
-    V[k][0] = m.vertex[3 * i], V[k][1] = m.vertex[3 * i + 1], V[k][2] = m.vertex[3 * i + 2], V[k][3] = 1.0f;
-  }
-}
 __device__ __forceinline__ void project_face(const DView& vw, int level, const float V[3][4], pmvstex::Corner* c) {
   for (int k = 0; k < 3; ++k) {
     float ic[3];

@@ -165,6 +165,25 @@ class TextureBuffers(C.Structure):  # pmvs_texture_buffers
     _fields_ = [(k, C.c_void_p) for k in ("view", "uv", "score")]
 
 
+class AtlasParams(C.Structure):  # pmvs_atlas_params
+    _fields_ = [("width", C.c_int32), ("max_side", C.c_int32), ("scale", C.c_float)]
+
+
+class AtlasLayout(C.Structure):  # pmvs_atlas_layout
+    _fields_ = [(k, C.c_int64) for k in ("width", "height", "placed", "cells")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class AtlasBuffers(C.Structure):  # pmvs_atlas_buffers
+    _fields_ = [(k, C.c_void_p) for k in ("rgb", "texel_face", "uv", "atlas_view")]
+
+
+ATLAS_MAX_SIDE = 251
+ATLAS_MAX_WIDTH = 65536
+
+
 class SeedStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("trial", "pass_", "fail0", "fail1", "refined", "rounds", "candidates",
                                           "reserved")] + [(k, C.c_double) for k in ("wall_ms", "gen_ms", "refine_ms")]
@@ -216,6 +235,7 @@ EXPORTS = ["pmvs_last_error", "pmvs_device_count", "pmvs_scene_create", "pmvs_sc
            "pmvs_loop_brick_tsdf", "pmvs_brick_tsdf_patches", "pmvs_brick_tsdf_mesh", "pmvs_loop_brick_mesh",
            "pmvs_brick_mesh_patches", "pmvs_brick_volume_from_points",
            "pmvs_mesh_raster", "pmvs_mesh_texture", "pmvs_write_ply_texmesh_binary",
+           "pmvs_mesh_atlas", "pmvs_atlas_layout_from_counts", "pmvs_write_ppm",
            "pmvs_loop_text", "pmvs_text_patches", "pmvs_selftest_format", "pmvs_selftest_labels",
            "pmvs_scene_set_shard", "pmvs_scene_set_shard_rccl", "pmvs_scene_set_cluster",
            "pmvs_scene_set_cluster_rccl", "pmvs_rccl_unique_id",
@@ -327,6 +347,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.pmvs_write_ply_texmesh_binary.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p),
                                                   C.c_void_p]
+    lib.pmvs_mesh_atlas.argtypes = [C.c_void_p, C.c_int32, C.POINTER(AtlasParams)] + texmesh_tail + \
+                                   [C.c_void_p, C.c_int64, C.POINTER(AtlasBuffers), C.POINTER(AtlasLayout)]
+    lib.pmvs_atlas_layout_from_counts.argtypes = [C.POINTER(AtlasParams), C.c_void_p, C.POINTER(AtlasLayout), C.c_void_p]
+    lib.pmvs_write_ppm.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.pmvs_loop_text.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                    C.POINTER(C.c_int64)]
     lib.pmvs_text_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -1075,6 +1099,39 @@ class Scene:
         del keep
         return out
 
+    # pmvs_atlas_buffers: h written rows of w texels; f faces
+    ATLAS_ARRAYS = {"rgb": ("uint8", ("h", "w", 3)), "texel_face": ("int32", ("h", "w")), "uv": ("float32", ("f", 6)),
+                    "atlas_view": ("int32", ("f",))}
+
+    def mesh_atlas(self, vertex, face, view, width: int = 8192, max_side: int = 64, scale: float = 1.0, device: bool = False,
+                   arrays=None, height_cap=None):
+        """pmvs_mesh_atlas: the mesh with mesh_texture's `view` [nf] baked into one atlas `width` texels wide:
+        every placed face gets a right triangle of side 1 .. max_side texels (`scale` texels per level-0 pixel
+        of its longest edge), two to a cell.  Returns (arrays, layout): the arrays keyed by the fields of
+        pmvs_atlas_buffers -- rgb [rows, width, 3] uint8, texel_face [rows, width] int32 (-1 = EMPTY), uv
+        [nf, 6] float32 (the corners in atlas texels), atlas_view [nf] int32 (0 = placed, -1 = not) -- and
+        the layout {width, height, placed, cells}.  rows = min(height, height_cap) (None: the whole atlas);
+        a sizing call comes first.  device=True: the mesh, the views and the arrays are torch tensors on the
+        scene's device.  arrays: the names wanted (None = all)."""
+        mesh, keep = self._mesh_inputs(vertex, face, device)
+        if device:
+            import torch
+            vw = torch.as_tensor(view, dtype=torch.int32, device=torch.device("cuda", self.device)).contiguous().reshape(-1)
+            vptr = vw.data_ptr() if vw.numel() else None
+        else:
+            vw = np.ascontiguousarray(view.cpu().numpy() if hasattr(view, "cpu") else view, np.int32).reshape(-1)
+            vptr = _ptr(vw) if vw.size else None
+        if len(vw) != mesh[2]:
+            raise ValueError("mesh_atlas takes one view per face")
+        prm, layout = AtlasParams(width, max_side, scale), AtlasLayout()
+        flags = self._flags(False, device)
+        _check(self.lib.pmvs_mesh_atlas(self.handle, flags, C.byref(prm), *mesh, vptr, 0, None, C.byref(layout)))
+        rows = int(layout.height) if height_cap is None else min(int(layout.height), int(height_cap))
+        out, buf = self._new_arrays(AtlasBuffers, self.ATLAS_ARRAYS, arrays, device, h=rows, w=width, f=mesh[2])
+        _check(self.lib.pmvs_mesh_atlas(self.handle, flags, C.byref(prm), *mesh, vptr, rows, C.byref(buf), C.byref(layout)))
+        del keep, vw
+        return out, layout.as_dict()
+
     def _text(self, call, writer_order, index2image, device: bool, out):
         """call(flags, index2image, out, cap, byref(size)): a size query, the buffer (numpy uint8, or a torch
         uint8 tensor on the scene's device; `out` supplies it) and the call that fills it; returns the
@@ -1359,6 +1416,25 @@ def write_pfm(path: str, data):
     if a.ndim != 2:
         raise ValueError("write_pfm takes a [height, width] array")
     _check(load_library().pmvs_write_pfm(path.encode(), a.shape[1], a.shape[0], _ptr(a)))
+
+
+def write_ppm(path: str, rgb):
+    """pmvs_write_ppm: a [height, width, 3] uint8 image (top row first) as a binary P6 PPM."""
+    a = np.ascontiguousarray(rgb, np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("write_ppm takes a [height, width, 3] array")
+    _check(load_library().pmvs_write_ppm(path.encode(), a.shape[1], a.shape[0], _ptr(a)))
+
+
+def atlas_layout_from_counts(counts, width: int, max_side: int, scale: float = 1.0):
+    """pmvs_atlas_layout_from_counts: (layout dict, band_y [max_side + 1]) of an atlas whose class n holds
+    counts[n] faces (counts has max_side + 1 entries; counts[0] is not read); band_y[0] = the height."""
+    c = np.ascontiguousarray(counts, np.int64)
+    if c.shape != (max_side + 1,):
+        raise ValueError("atlas_layout_from_counts takes max_side + 1 counts")
+    prm, layout, band_y = AtlasParams(width, max_side, scale), AtlasLayout(), np.zeros(max_side + 1, np.int64)
+    _check(load_library().pmvs_atlas_layout_from_counts(C.byref(prm), _ptr(c), C.byref(layout), _ptr(band_y)))
+    return layout.as_dict(), band_y
 
 
 def depth_map_view(array, dims, offsets, t: int):

@@ -848,6 +848,98 @@ pmvs_status pmvs_write_ply_texmesh_binary(const char* path, int64_t nv, const fl
                                           const float* uv, int32_t ntex, const char* const* tex_files,
                                           const int32_t* tex_dims);
 
+/* THE ATLAS: the textured mesh baked into one image.  pmvs_mesh_atlas cuts every face's texels out of the view
+ * pmvs_mesh_texture chose for it and packs them into one W-texel-wide RGB image, so that the model travels
+ * with one texture instead of its input images.  Only the device, the stream, the views and the level-0 images
+ * are taken from the scene.  There is no reference for this; csrc/pmvs_atlas.h implements what follows once,
+ * for host and device.  All f64 arithmetic is unfused, from the f32 inputs, sums left to right in the order
+ * written.
+ *
+ * Inputs: the mesh (vertex nv x 3 f32, face nf x 3 int32), view (nf int32, as pmvs_mesh_texture returns it: a
+ * scene target index in [0, num_targets) or -1) and the parameters width W, max_side M and scale.
+ *  1. CORNERS.  For face f with view(f) = t >= 0 and corner k: (x_k, y_k, w_k) = CCamera::project(view t,
+ *     (V_k, 1.0f), 0): level-0 pixels, pmvs_mesh_texture's uv.  f is PLACED iff t >= 0, the three w_k > 0 and
+ *     the six coordinates are finite.
+ *  2. SIDE.  e = the greatest of |x_a - x_b| and |y_a - y_b| over the three edges (differences in f64; a
+ *     Chebyshev length, no square root), s = (double)scale * e, n(f) = 1 if s <= 1, M if s >= M, else
+ *     (int)ceil(s).
+ *  3. ORDER.  The placed faces of side n, by ascending face id, have ranks r = 0, 1, ... within their class;
+ *     slot = r >> 1, half = r & 1: two faces share one square cell.
+ *  4. BANDS.  Classes are laid out from n = M down to 1.  For class n: c = n + 5, k = W / c cells per row,
+ *     slots = (count_n + 1) >> 1, rows = ceil(slots / k), y_n = the sum over the classes m > n of
+ *     rows_m * (m + 5); slot s has the cell origin (ox, oy) = ((s % k) * c, y_n + (s / k) * c).  The atlas
+ *     height H = the sum over all classes of rows_n * (n + 5); 0 if nothing is placed.
+ *  5. TRIANGLES.  Texel centres are at integers (uv's convention, so pmvs_write_ply_texmesh_binary applies
+ *     unchanged).  Relative to the cell origin, half 0 has the corners T0 = (1, 1), T1 = (1 + n, 1),
+ *     T2 = (1, 1 + n); half 1 has T0 = (c - 2, c - 2), T1 = (c - 2 - n, c - 2), T2 = (c - 2, c - 2 - n).
+ *     Texel (i, j) of the cell belongs to half 0 iff i + j <= n + 3, otherwise to half 1.  A bilinear fetch
+ *     at any point of a triangle then touches, with non-zero weight, only texels of its own half of its own
+ *     cell; column and row 0 are pure gutter of half 0, column and row c - 1 of half 1.
+ *  6. TEXEL -> COLOUR.  Texel (I, J) of the atlas: the band that contains row J, the cell row (J - y_n) / c,
+ *     the column I / c, hence the slot and (i, j) = (I - ox, J - oy) and the half.  The texel is EMPTY when
+ *     I / c >= k, when the slot is >= slots, when its half holds no face (the last slot of a class with an
+ *     odd count), or when J >= H: texel_face = -1, colour (0, 0, 0).  Otherwise f is its face and, for half 0,
+ *     l1 = (double)(i - 1) / n, l2 = (double)(j - 1) / n; for half 1, l1 = (double)(c - 2 - i) / n,
+ *     l2 = (double)(c - 2 - j) / n; l0 = 1.0 - l1 - l2; X_a = (float)(l0 * V0_a + l1 * V1_a + l2 * V2_a);
+ *     (x, y, w) = project(view(f), (X, 1.0f), 0): through the face's plane, so perspective-correct; gutter
+ *     texels extrapolate on the same plane.  If w <= 0 or x or y is not finite the colour is (0, 0, 0).
+ *     Otherwise xs = x clamped to [0, W0 - 2], ys = y clamped to [0, H0 - 2] (compared in double, the bounds
+ *     as f32; W0 x H0 = view(f)'s level-0 image), rgb = CImage::getColor's bilinear arithmetic
+ *     (image.hpp:435-476) on that image at (xs, ys), and each byte = min(255, floor(c + 0.5f)),
+ *     pmvs_patch_colors' rounding.  The clamp gives up at most the last column and row of a source image.
+ *  7. OUTPUTS.  rgb: H x W x 3 bytes, top row first.  texel_face: H x W int32.  uv: nf x 6 f32, for a placed
+ *     face the three corners (float)(ox + T_k.x), (float)(oy + T_k.y), zeros for any other face.  atlas_view:
+ *     nf int32, 0 for a placed face and -1 otherwise: what pmvs_write_ply_texmesh_binary takes as `view` with
+ *     ntex = 1 and tex_dims = {W, H}.  Any pointer may be NULL (and buffers itself: nothing is wanted).  Only
+ *     the first min(H, height_cap) rows of the two images are written and nothing past them; height_cap = 0
+ *     with NULL image pointers is the sizing call.  *layout = {W, H, placed faces, cells (the sum of slots)}.
+ *     Nothing depends on the order of the work.
+ *
+ * flags: only PMVS_EXPORT_DEVICE; with it every array pointer (vertex, face, view and the buffers') is a device
+ * pointer on the scene's device.  PMVS_EINVAL: a NULL scene, params or layout; another flag bit; max_side
+ * outside 1..PMVS_ATLAS_MAX_SIDE; width outside [max_side + 5, PMVS_ATLAS_MAX_WIDTH]; scale not finite or
+ * <= 0; nv or nf negative or above 2^31-1; a NULL array with a positive count; a negative height_cap; a source
+ * image narrower or lower than 2 pixels at level 0; a face id outside [0, nv) or a view outside
+ * [-1, num_targets) (host arrays are checked before the device is touched, device arrays by a kernel whose one
+ * flag is read back before any value is used as an index).  PMVS_EUNSUPPORTED when H exceeds 2^31-1 (*layout is
+ * still filled, its fields saturated at 2^63-1).  PMVS_ENOMEM when the device cannot hold the scratch: per face 10 bytes (two class bytes, the
+ * face id and its place in the class order) and the radix sort's temporary storage (about 5 more); nothing per
+ * texel; in host mode also the mesh (12 bytes per vertex, 16 per face) and the requested outputs (7 bytes per
+ * written texel, 28 per face).  All of it is allocated for the call and freed on return; the call returns
+ * after its work has finished.
+ *
+ * pmvs_atlas_layout_from_counts is step 4 alone, on the host: counts[n], n = 1..max_side, = the placed faces
+ * of side n (counts[0] is not read); band_y (max_side + 1 entries, may be NULL) receives y_n, band_y[0] = H.
+ * PMVS_EINVAL for a NULL params, counts or layout, the parameters' ranges above, a negative count;
+ * PMVS_EUNSUPPORTED when H exceeds 2^31-1.  pmvs_mesh_atlas calls it on its histogram. */
+#define PMVS_ATLAS_MAX_SIDE  251    /* so that a cell is at most 256 texels */
+#define PMVS_ATLAS_MAX_WIDTH 65536
+typedef struct pmvs_atlas_params {
+  int32_t width;     /* W: max_side + 5 .. PMVS_ATLAS_MAX_WIDTH texels */
+  int32_t max_side;  /* M: 1 .. PMVS_ATLAS_MAX_SIDE */
+  float   scale;     /* finite, > 0: atlas texels per level-0 pixel of a face's longest edge */
+} pmvs_atlas_params;
+
+typedef struct pmvs_atlas_layout {
+  int64_t width;   /* W */
+  int64_t height;  /* H */
+  int64_t placed;  /* faces with a triangle in the atlas */
+  int64_t cells;   /* square cells in use */
+} pmvs_atlas_layout;
+
+typedef struct pmvs_atlas_buffers {  /* any pointer may be NULL: that array is skipped */
+  uint8_t* rgb;         /* min(H, height_cap) x W x 3 */
+  int32_t* texel_face;  /* min(H, height_cap) x W: the texel's face, -1 = EMPTY */
+  float*   uv;          /* nf x 6: the corners in atlas texels */
+  int32_t* atlas_view;  /* nf: 0 = placed, -1 = not */
+} pmvs_atlas_buffers;
+
+pmvs_status pmvs_mesh_atlas(pmvs_scene* scene, int32_t flags, const pmvs_atlas_params* params, int64_t nv,
+                            const float* vertex, int64_t nf, const int32_t* face, const int32_t* view,
+                            int64_t height_cap, const pmvs_atlas_buffers* buffers, pmvs_atlas_layout* layout);
+pmvs_status pmvs_atlas_layout_from_counts(const pmvs_atlas_params* params, const int64_t* counts,
+                                          pmvs_atlas_layout* layout, int64_t* band_y);
+
 /* The .ply / .patch / .pset text of the model, formatted on the device: the bytes pmvs_write_ply /
  * pmvs_write_patches / pmvs_write_pset write from the export of the same records and flags
  * (CPatchOrganizerS::writePLY patchOrganizerS.cpp:687-776, writePatches2 :89-132 with Patch::operator<<
@@ -1030,6 +1122,10 @@ pmvs_status pmvs_write_ply(const char* path, int32_t n, const float* fields, con
  * then the rows from the bottom one to the top one as little-endian float32.  PMVS_EINVAL for a NULL
  * argument, a non-positive size or a file that cannot be written. */
 pmvs_status pmvs_write_pfm(const char* path, int32_t width, int32_t height, const float* data);
+/* A binary 8-bit PPM of width x height RGB pixels given top row first (pmvs_mesh_atlas's rgb): the header
+ * "P6\n<width> <height>\n255\n", then the bytes as given; what pmvs_ppm_load reads back.  PMVS_EINVAL for a
+ * NULL argument, a non-positive size or a file that cannot be written. */
+pmvs_status pmvs_write_ppm(const char* path, int32_t width, int32_t height, const uint8_t* rgb);
 /* writePLY colour mode 0 on the device: mean of CPhotoSetS::getColor over the patch's images at
  * the scene level, floor(c + 0.5) clamped to 255.  images_flat holds nimg[i] view indexes per patch. */
 pmvs_status pmvs_patch_colors(pmvs_scene* scene, int32_t n, const float* coords4, const int32_t* nimg,
